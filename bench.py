@@ -6,13 +6,19 @@ architectures, deterministic synthetic weights, synthetic audio; one step = FXen
 (all-gather of segment embeddings when N > 1) -> mean -> FiLM factors -> TCN on the 32 input segments.  Inputs are
 resident in HBM before the timed region.  Weak scaling: every rank owns 32 segments.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision bf16|fp32] [--workload all|configs1|track60]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision bf16|fp32] [--workload all|configs1|track60] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line (rank 0), kept under 4 KB so that it survives any log tail: per leg only value / ms / frac / max_abs_vs_oracle.
-Everything else (per-block times, thread sweeps, workload prose, the normaliser's per-effect times) goes to the DETAILS file the line names
-("details": gpurun_out/bench_details.json, also copied to profiles/ by tools/gpu_round.sh).  Objects carried by the line:
+A plain run measures the headline only: set-up, W warm-up steps, K timed steps, the outputs of the last timed step when
+--dump-outputs DIR is given (DIR/<name>.npy, float32, at most DUMP_BYTES in all), then ONE JSON line (rank 0) with metric / value /
+unit / ms_per_step.  Every other figure below (per-kernel roofline, box calibration, the other legs, precisions, the CPU baseline and the
+comparisons with the oracle) is measured only with --full.
+
+With --full the line (kept under 4 KB so that it survives any log tail) carries per leg only value / ms / frac / max_abs_vs_oracle.
+Everything else (per-block times, thread sweeps, workload prose, the normaliser's per-effect times) goes to the DETAILS file the line
+names ("details": the path of DETAILS_PATH relative to the repository).  Objects carried by the --full line:
   "roofline"      dominant kernel = the dilated 128x128x15 TCN block conv, timed with HIP events on its stream inside
                   the timed region;
   "track60"       BASELINE configs[4]: ONE 60-minute stereo stem (158 760 000 samples = 1212 segments of 131072 for the
@@ -26,7 +32,7 @@ Everything else (per-block times, thread sweeps, workload prose, the normaliser'
   "bf16x3_mode"   (N = 1) the same step in the split-bf16 mode (three bf16 MFMAs per product): <= 1e-4 as well, at bf16-MFMA speed / 3;
   "fx_chain"      (N = 1) BASELINE configs[3]: EQ -> rms -> compressor -> rms -> imager -> rms -> gain on 64 segments;
   "cpu_baseline"  (N = 1) the oracle (torch-CPU restatement of the reference) on a bounded sample, all cores and 1 thread.
-With --workload track60 the track IS the headline ("scaling": "strong").
+With --workload track60 the track IS the headline ("scaling": "strong"); its pcie_inclusive and t1_ms_same_job figures need --full.
 """
 import argparse
 import ctypes as C
@@ -51,6 +57,26 @@ HBM_PEAK_GBPS = 8000.0
 
 
 DETAILS_PATH = os.path.join(REPO, "gpurun_out", "bench_details.json")
+DUMP_BYTES = 60_000_000                                 # --dump-outputs: bytes written in all (under 64 MB)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every tensor of `arrays` (name -> tensor) as path/<name>.npy in float32.  The smaller tensors are written
+    whole; one that exceeds its share of DUMP_BYTES is replaced by a fixed sample of its flattened elements (sorted indices drawn
+    with seed 0 from the tensor's size alone, so that two builds of the project compare element for element)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    left = DUMP_BYTES
+    for i, (name, t) in enumerate(items):
+        share = left // (len(items) - i)
+        t = t.detach()
+        if t.numel() * 4 > share:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), share // 4, dtype=np.int64))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
 
 
 class BoxSampler:
@@ -170,13 +196,15 @@ def cpu_baseline(enc_cfg, enc_sd, tcn_sd):
 
 
 # ------------------------------------------------------------------------------------------------ configs[1] step
-def bench_configs1(engine, tcn, lib, ref, inp, steps, warmup, world, dist, dev, stats=None):
-    """K timed steps between barriers; returns (seconds max over ranks, per-block kernel ms, forwards timed).  stats (a dict) also
-    receives the per-step durations (HIP events on the stream the steps run on) and the clock / power samples of the region."""
+def bench_configs1(engine, tcn, lib, ref, inp, steps, warmup, world, dist, dev, stats=None, per_block=True):
+    """K timed steps between barriers; returns (seconds max over ranks, per-block kernel ms, forwards timed, (y, embedding) of the last
+    step).  per_block=False leaves the TCN's timing hook off (per-block ms None, forwards timed 0).  stats (a dict) also receives the
+    per-step durations (HIP events on the stream the steps run on) and the clock / power samples of the region."""
     for _ in range(warmup):
         engine.step(ref, inp)
     torch.cuda.synchronize()
-    lib.check(lib.mst_tcn_timing_begin(tcn._handle, steps), "timing_begin")
+    if per_block:
+        lib.check(lib.mst_tcn_timing_begin(tcn._handle, steps), "timing_begin")
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)] if stats is not None else None
     sampler = BoxSampler(dev.index if dev.index is not None else 0) if stats is not None else None
     if world > 1:
@@ -185,10 +213,12 @@ def bench_configs1(engine, tcn, lib, ref, inp, steps, warmup, world, dist, dev, 
     if sampler is not None:
         sampler.__enter__()
     t0 = time.perf_counter()
+    last = None
     for k in range(steps):
         if marks is not None:
             marks[k].record()
-        engine.step(ref, inp)
+        last = None                 # the previous step's outputs go first, so that every step reuses the same cached blocks
+        last = engine.step(ref, inp)
     if marks is not None:
         marks[steps].record()
     torch.cuda.synchronize()
@@ -200,16 +230,19 @@ def bench_configs1(engine, tcn, lib, ref, inp, steps, warmup, world, dist, dev, 
         per = [marks[k].elapsed_time(marks[k + 1]) for k in range(steps)]
         stats["step_ms"] = {"median": statistics.median(per), "min": min(per), "max": max(per)}
         stats["box"] = sampler.summary()
-    nb = tcn.hparams.nblocks
-    ms = (C.c_float * (nb + 1))()
-    nf = C.c_int(0)
-    lib.check(lib.mst_tcn_timing_end(tcn._handle, ms, C.byref(nf)), "timing_end")
+    block_ms, nf = None, 0
+    if per_block:
+        nb = tcn.hparams.nblocks
+        ms = (C.c_float * (nb + 1))()
+        nfc = C.c_int(0)
+        lib.check(lib.mst_tcn_timing_end(tcn._handle, ms, C.byref(nfc)), "timing_end")
+        block_ms, nf = [float(v) for v in ms], int(nfc.value)
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     if stats is not None:
         stats["fused0"] = tcn_fused_block0(lib, tcn)
-    return float(tmax.item()), [float(v) for v in ms], int(nf.value)
+    return float(tmax.item()), block_ms, nf, last
 
 
 KERNEL_SOURCES = {"tcn": ("tcn_kernels.h", "mst_dev.h", "mst_rt.h"), "fx": ("fx_kernels.h", "fft_kernels.h", "mst_dev.h", "mst_rt.h")}
@@ -287,7 +320,8 @@ def slim_roofline(rl):
 
 # ------------------------------------------------------------------------------------------------ 60-minute track
 def bench_track60(enc, tcn, world, rank, dist, dev, steps, warmup, with_host=True, with_t1=True):
-    """One 60-minute stem (reference + input role), its 1212 segments split over the ranks."""
+    """One 60-minute stem (reference + input role), its 1212 segments split over the ranks.  Returns (figures, the converted stem
+    - this rank's shard when N > 1 - of the last timed pass with the stems resident in HBM)."""
     from music_mixing_style_transfer_amd.inference import StyleTransferEngine
     from music_mixing_style_transfer_amd.inference import segmentation as seg
     g = torch.Generator(device=dev).manual_seed(1234)             # the same track on every rank
@@ -303,8 +337,10 @@ def bench_track60(enc, tcn, world, rank, dist, dev, steps, warmup, with_host=Tru
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        y = None
         for _ in range(k):
-            engine.transfer_stem(a, b, SEG_LEN, SEG_LEN)
+            y = None                # the previous pass's stem goes first, so that every pass reuses the same cached blocks
+            y = engine.transfer_stem(a, b, SEG_LEN, SEG_LEN)
         torch.cuda.synchronize()
         if sync_ranks:
             dist.barrier()
@@ -313,10 +349,10 @@ def bench_track60(enc, tcn, world, rank, dist, dev, steps, warmup, with_host=Tru
             t = torch.tensor([dt], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        return dt
+        return dt, y
 
     eng = StyleTransferEngine(enc, tcn)
-    t_res = timed(eng, x_in, x_ref, steps, warmup, world > 1)
+    t_res, y_res = timed(eng, x_in, x_ref, steps, warmup, world > 1)
     lo, hi = seg.shard_range(n_seg, rank, world)
     out = {"workload": f"configs[4]: one 60-min stereo stem = {n_seg} segments of 2x{SEG_LEN} (reference and input role), "
                        f"contiguous segment shards over {world} GPU(s), all-gather of [{n_seg}, 2048] embeddings, "
@@ -325,7 +361,7 @@ def bench_track60(enc, tcn, world, rank, dist, dev, steps, warmup, with_host=Tru
            "value": n_seg / t_res, "unit": "segments/s", "t_ms": t_res * 1e3}
     if with_host:
         h_in, h_ref = x_in.cpu().pin_memory(), x_ref.cpu().pin_memory()
-        t_host = timed(eng, h_in, h_ref, max(1, steps // 2), 1, world > 1)
+        t_host, _ = timed(eng, h_in, h_ref, max(1, steps // 2), 1, world > 1)
         out["pcie_inclusive"] = {"value": n_seg / t_host, "unit": "segments/s", "t_ms": t_host * 1e3,
                                  "what": "stems in pinned host memory -> each rank uploads / converts / downloads only its "
                                          "shard (copy streams overlap the networks) -> converted shard in pinned host memory"}
@@ -334,11 +370,11 @@ def bench_track60(enc, tcn, world, rank, dist, dev, steps, warmup, with_host=Tru
         if rank == 0:
             solo = StyleTransferEngine(enc, tcn)
             solo.dist, solo.world, solo.rank = None, 1, 0          # the same track on this GPU alone
-            t1 = timed(solo, x_in, x_ref, 1, 1, False)
+            t1, _ = timed(solo, x_in, x_ref, 1, 1, False)
             out["t1_ms_same_job"] = t1 * 1e3
             out["efficiency_t1_over_n_tn"] = t1 / (world * t_res)
         dist.barrier()
-    return out
+    return out, (y_res[0] if isinstance(y_res, tuple) else y_res)
 
 
 # ------------------------------------------------------------------------------------------------ parity mode (fp32)
@@ -348,7 +384,7 @@ def bench_parity_mode(engine, enc, tcn, lib, ref, inp, dev, enc_cfg, enc_sd, tcn
     enc.precision = tcn.precision = precision
     try:
         nsteps = 2 if precision == "fp32" else 4
-        dt, block_ms, _ = bench_configs1(engine, tcn, lib, ref, inp, nsteps, 2, 1, None, dev)
+        dt, block_ms, _, _ = bench_configs1(engine, tcn, lib, ref, inp, nsteps, 2, 1, None, dev)
         fused0 = tcn_fused_block0(lib, tcn)
         L = 16384
         pr, pi = synth.synth_audio((2, 2, L), seed=5), synth.synth_audio((2, 2, L), seed=6)
@@ -482,6 +518,9 @@ def main():
     ap.add_argument("--enc-schedule", type=int, default=None, help="mst_enc_set_schedule flags (bit 0: weight-major workgroup order of the weight-heavy encoder layers, bit 1: 2 x 2 wave tiling of the 128-channel conv kernel)")
     ap.add_argument("--enc-rows-min-tiles", type=int, default=None, help="mst_enc_set_tuning: tiles from which a layer keeps its rows resident in LDS (-1 never)")
     ap.add_argument("--tcn-tuning", type=int, default=None, help="mst_tcn_set_tuning flags (bit 0: bf16x3 small tiles, bits 1-2: form of the bf16 block kernel, include/mst_hip.h)")
+    ap.add_argument("--full", action="store_true", help="every figure besides the headline: roofline, calibration, the other legs and precisions, "
+                                                         "CPU baseline, oracle comparisons, details file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -571,7 +610,10 @@ def main():
         return [int(g.item()) for g in got]
 
     if args.workload == "track60":
-        tr = bench_track60(enc, tcn, world, rank, dist, dev, args.steps, args.warmup)
+        tr, y_last = bench_track60(enc, tcn, world, rank, dist, dev, args.steps, args.warmup, with_host=args.full, with_t1=args.full)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"y": y_last})
+        del y_last
         tr["segments_rank"] = per_rank(tr["segments_rank_local"])
         if rank == 0:
             out = dict(base, metric="stereo 44.1 kHz segments/sec (FXencoder+MixFXcloner fwd)", value=tr["value"],
@@ -585,12 +627,33 @@ def main():
 
     ref = synth.synth_audio((B, 2, SEG_LEN), seed=100 + rank).to(dev)      # resident in HBM before timing
     inp = synth.synth_audio((B, 2, SEG_LEN), seed=200 + rank).to(dev)
-    stats = {}
-    dt, block_ms, nf = bench_configs1(engine, tcn, lib, ref, inp, args.steps, args.warmup, world, dist, dev, stats)
+    stats = {} if args.full else None
+    dt, block_ms, nf, (y_last, emb_last) = bench_configs1(engine, tcn, lib, ref, inp, args.steps, args.warmup, world, dist, dev, stats,
+                                                          per_block=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"y": y_last, "embedding": emb_last})
+    del y_last, emb_last
+
+    def headline(seg_rank):
+        workload = (f"configs[1]: batch={B} segments of 2x{SEG_LEN} per GPU, FXencoder+MixFXcloner fwd, default configs.yaml nets, "
+                    f"synthetic weights, {args.precision} MFMA (fp32 accumulate)")
+        return dict(base, metric="stereo 44.1 kHz segments/sec (FXencoder+MixFXcloner fwd)",
+                    value=world * B * args.steps / dt, unit="segments/s", ms_per_step=dt / args.steps * 1e3, scaling="weak",
+                    config={"workload": workload, "segments_per_gpu": B, "segment_length": SEG_LEN, "segments_rank": seg_rank,
+                            "parallelism": f"segment-sharded x{world}, all-gather of embeddings"})
+
+    if not args.full:
+        seg_rank = per_rank(B)
+        if rank == 0:
+            print(json.dumps(headline(seg_rank)), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     calib_ms, calib_mhz = calibrate(lib, dev) if args.precision == "bf16" else (None, None)      # right behind the timed region: the chip is warm
     track = None
     if args.workload == "all" and args.precision == "bf16":
-        track = bench_track60(enc, tcn, world, rank, dist, dev, 2, 1)
+        track, _ = bench_track60(enc, tcn, world, rank, dist, dev, 2, 1)
         track["segments_rank"] = per_rank(track["segments_rank_local"])
     seg_rank = per_rank(B)
 
@@ -612,12 +675,7 @@ def main():
             rl["calib_sclk_mhz"] = round(calib_mhz)
         rl.update(stats.get("box", {}))
         details = {"headline": {"roofline": dict(rl), "step_ms": stats.get("step_ms")}}
-        workload = (f"configs[1]: batch={B} segments of 2x{SEG_LEN} per GPU, FXencoder+MixFXcloner fwd, default configs.yaml nets, "
-                    f"synthetic weights, {args.precision} MFMA (fp32 accumulate)")
-        out = dict(base, metric="stereo 44.1 kHz segments/sec (FXencoder+MixFXcloner fwd)",
-                   value=world * B * args.steps / dt, unit="segments/s", ms_per_step=dt / args.steps * 1e3, scaling="weak",
-                   config={"workload": workload, "segments_per_gpu": B, "segment_length": SEG_LEN, "segments_rank": seg_rank,
-                           "parallelism": f"segment-sharded x{world}, all-gather of embeddings"},
+        out = dict(headline(seg_rank),
                    step_ms={k: round(v, 3) for k, v in (stats.get("step_ms") or {}).items()},
                    roofline=slim_roofline(rl))
         if world == 1 and args.precision in ("bf16", "bf16x3"):

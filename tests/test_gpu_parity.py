@@ -1501,7 +1501,7 @@ def test_fx_manipulator_chains_and_algorithmic_reverb_on_gpu(tmp_path):
 def test_bench_two_ranks_gloo_prints_the_strong_scaling_efficiency():
     """`python bench.py --gpus 2 ...` typed exactly like the driver's N = 1 command (NO torchrun in front, no WORLD_SIZE in the environment):
     bench.py starts its own two ranks (here sharing this box's one GPU, gloo for the collective) and rank 0 prints the ONE line - the N > 1
-    code path of the bench: sharded track, all-gather, max over ranks, T1 of the same job on rank 0; the line carries ranks_seen,
+    code path of the bench: sharded track, all-gather, max over ranks, T1 of the same job on rank 0 (--full); the line carries ranks_seen,
     t1_ms_same_job and efficiency_t1_over_n_tn = T1 / (N * TN).  Two ranks on ONE GPU cannot exceed 0.5 by construction - this checks the
     plumbing, not the scaling; no multi-GPU curve has been measured on hardware (README)."""
     import json
@@ -1510,7 +1510,7 @@ def test_bench_two_ranks_gloo_prints_the_strong_scaling_efficiency():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MST_BENCH_SHARE_GPU="1", MST_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-                        "--workload", "track60"], env=env, capture_output=True, text=True, timeout=900, cwd=REPO)
+                        "--workload", "track60", "--full"], env=env, capture_output=True, text=True, timeout=900, cwd=REPO)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

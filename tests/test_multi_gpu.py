@@ -52,8 +52,9 @@ def test_nccl_sharded_stem_is_bit_equal_to_one_gpu(precision):
 @pytest.mark.gpu
 @pytest.mark.skipif(_n_gpus() < 2, reason="needs >= 2 GPUs (RCCL with more than one rank)")
 def test_bench_two_gpus_over_rccl():
-    """`python bench.py --gpus 2 --workload track60` exactly as the driver types it (bench.py starts its own ranks): one rank per GPU, nccl."""
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "track60"],
+    """`python bench.py --gpus 2 --workload track60 --full` (bench.py starts its own ranks): one rank per GPU, nccl."""
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "track60",
+                        "--full"],
                        env=_clean_env(), capture_output=True, text=True, timeout=1500, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -2,7 +2,7 @@
 # same-box A/B of two builds (tools/_ab/old.so, tools/_ab/new.so) on the split-bf16 headline with per-block kernel times
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/ab; mkdir -p $O
-one() { python bench.py --precision bf16x3 --workload configs1 --steps 4 --warmup 2 --no-cpu-baseline 2>$O/err_x3.txt | python -c "
+one() { python bench.py --full --precision bf16x3 --workload configs1 --steps 4 --warmup 2 --no-cpu-baseline 2>$O/err_x3.txt | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); x=json.load(open('gpurun_out/bench_details.json'))['details']['headline']['roofline']
 print(round(d['value'],1), round(d['ms_per_step'],3), [round(v,3) for v in x['per_block_ms']])"; }

@@ -1,9 +1,9 @@
 #!/bin/bash
-# N = 1, 2, 4, 8 back to back on ONE node (python bench.py --gpus N starts its own N ranks over RCCL): the weak-scaling value (configs[1] per GPU) and the
+# N = 1, 2, 4, 8 back to back on ONE node (python bench.py --full --gpus N starts its own N ranks over RCCL): the weak-scaling value (configs[1] per GPU) and the
 # strong-scaling efficiency of the 60-minute stem (track60.efficiency_t1_over_n_tn) per N.  No curve has been measured yet: the pool's boxes have one GPU.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"; O=gpurun_out/scale; mkdir -p $O; export HSA_ENABLE_IPC_MODE_LEGACY=0
 for n in ${NS:-1 2 4 8}; do
-  timeout 1800 python bench.py --gpus $n --steps ${STEPS:-20} --warmup ${WARMUP:-5} > $O/bench_n$n.json 2> $O/bench_n$n.err || echo "N=$n: rc=$?"
+  timeout 1800 python bench.py --full --gpus $n --steps ${STEPS:-20} --warmup ${WARMUP:-5} > $O/bench_n$n.json 2> $O/bench_n$n.err || echo "N=$n: rc=$?"
 done
 python - <<'PY'
 import glob, json, re
