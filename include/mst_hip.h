@@ -112,23 +112,24 @@ int mst_tcn_forward(MstTcn *tcn, const float *x_dev, float *y_dev, int B, int L,
 int mst_tcn_forward_blocks(MstTcn *tcn, const float *x_dev, float *act_dev, int B, int L, int precision, int n_run,
                            void *workspace, size_t workspace_bytes, void *stream);
 
-/* ---- Kernel-form switches at a glance (round 6) ------------------------------------------------------------------------------------------
+/* ---- Kernel-form switches at a glance ------------------------------------------------------------------------------------------------------
  * None of them changes WHAT is computed; "=" bit-identical to the default, "~" equal up to fp32 summation order.  The library keeps no
  * process-wide switch: every one lives in a handle or in the arguments of one call.  Defaults are the measured-fastest forms.
  *
  *   where                          bit / field            default  selects                                                  result  why it is still here
  *   mst_tcn_set_tuning (handle)    bit 0                  1        bf16x3: 128-time tiles of <= 2 phases, 2 workgroups / CU   ~       256-time form needed where < 64 steps per phase
- *                                  bits 1-2 = 2           2        bf16: 256-time class-major tiles - the one-tile kernel     ~/=     form 0 (tap-major one-tile kernel) runs what neither takes (odd d, short segments) and is
- *                                                                  with bit 7, else the persistent duo kernel                         the other side of GPU / emulator tests
- *                                  bit 3, form 1          -        (removed kernels: rejected with MST_ERR_ARG)
- *                                  bit 4                  1        bf16 duo: class-major main loop                           ~       tap-major loop = the P = 1 path and the GPU test's other side
- *                                  bit 5                  1        bf16: block 0 inside the d = 2 block's launch             =       separate block-0 kernel = probes, other precisions, short segments
+ *                                  bits 1-2               2        bf16: 2 = the class-major family - two- / four-phase       ~       0 = tcn_block_bf16_kernel's tap-major loop for every
+ *                                                                  blocks on 256-time class-major tiles, 2 workgroups / CU;           bf16 block: the reference form of the tests
+ *                                                                  1 and 3 rejected (MST_ERR_ARG)
+ *                                  bit 3                  0        rejected (MST_ERR_ARG)
+ *                                  bit 4                  1        required with form 2 (form 2 without it: MST_ERR_ARG); ignored with form 0
+ *                                  bit 5                  1        bf16, form 2: block 0 inside the d = 2 block's launch      =       separate block-0 kernel = probes, other precisions, short segments
  *                                  bit 6                  1        bf16x3: class-major loop in the eight-phase half kernel    ~       other side of a GPU test
- *                                  bit 7                  1        bf16: two- / four-phase class-major blocks, one 256-time   =/~     the duo kernel is the other side of the bit-identity tests (emulator + GPU
- *                                                                  tile per workgroup, two workgroups per CU (round 6)                forms 181 / 53) and what bit 7 off selects
+ *                                  bit 7                  1        bf16, form 2: whole-sequence 256-time tiles and the        =/~     off = those blocks on the general tilings and the
+ *                                                                  class-major fused head of a four-phase last block                  tap-major head: the other side of the tests
  *   mst_enc_set_tuning (handle)    rows_min_tiles         512      bf16: rows-resident conv kernel from this many tiles on    =       small layers run the im2col kernel
  *   mst_enc_set_schedule (handle)  bit 0                  1        weight-major workgroup order of weight-heavy layers        =
- *                                  bit 1                  0        2 x 2 wave tiling of the 128-channel kernel (slower)       ~       A/B record only
+ *                                  bit 1                  0        rejected (MST_ERR_ARG)
  *                                  bit 2                  0        fp32: 64-bit gather addresses                              =       the path > 4 GiB activations take anyway (test hook)
  *                                  bit 3                  0        stereo block as two direct launches                        =       reference form of the fused kernel's bit-identity test
  *                                  bit 4                  0        blocks 1 / 2 as two launches each                          ~       reference form of the fused kernel's test
@@ -136,51 +137,19 @@ int mst_tcn_forward_blocks(MstTcn *tcn, const float *x_dev, float *act_dev, int 
  *   MstFxFuse.forms (per call)     EQ_LANE_APPLY          0        stereo equaliser apply pass, one lane per chunk            =       reference form of a GPU / emulator test; non-stereo path
  *                                  EQ_VALU_ENDS           0        stereo equaliser state pass on VALU dot products           =       reference form; chunk lengths that are no multiple of 16
  *                                  COMP_SLICE_SMALL       0        compressor: three time slices whatever the size            =       lets small emulated problems take the pipelined path
- * (mst_fx_set_tuning - a process-wide switch - left the ABI in round 6.)
  * ------------------------------------------------------------------------------------------------------------------------------------------ */
-/* tuning flags (choose between forms of the block kernels; flags = x3_small_tiles | bf16_form << 1 | bf16_reuse << 4 | bf16_fuse0 << 5 |
- * x3_half_cm << 6 | bf16_onetile << 7, default 245; bit 3 and form 1 named kernels that were measured slower and left the library in round 5 - they are rejected):
- * bit 0 (bf16x3 mode; default 1, measured 5.13 instead of 5.45 ms per launch at 32 x 131072): the split-bf16 block kernel on 128-time
- *   tiles of <= 2 phases (two workgroups per CU) wherever the segment has at least 64 steps per phase, 0 = 256-time tiles (one
- *   workgroup per CU); the two-phase 128-time tiles run the class-major loop (B fragment pairs reused by the two taps of a class: 4.62 ->
- *   4.09 ms per launch, round 4), the 256-time tiles the tap-major one: results agree to fp32 accumulation rounding (~1e-6).
- * bits 1-2 (bf16 mode), form of the dense block kernel - measured at 32 x 131072, profiles/r03_tcn_block_forms_summary.md:
- *   0 tcn_block_bf16_kernel: one tile per workgroup, two workgroups per CU                                              1.49-1.51 ms
- *   2 (default) the blocks with 256-time tiles of <= 4 phases on the class-major family: with bit 7 (default since round 6) the one-tile kernel at
- *     two workgroups per CU (1.28-1.33 ms, see bit 7), else tcn_block_bf16_duo_kernel (form 0 for the others and for the last
- *     block): persistent, one workgroup of 4 matrix waves + 4 loader waves per CU, two tile buffers, the next tile by LDS-DMA and
- *     the previous tile's row stores during the main loop; with bit 4 off bit-identical to form 0                        1.47-1.48 ms (1.40 with bit 4)
- *   (1 was tcn_block_bf16_stream_kernel, 1.67 ms; bit 3 tcn_block_bf16x3_duo_kernel, 5.45-5.6 ms per launch against 4.09: EXPERIMENTS.md)
- * bit 4 (bf16 mode, form 2; default 1): the duo kernel's main loop runs class-major - taps grouped by j mod (16 / phases), every B
- *   fragment read from LDS once per class and k-step and fed to up to eight MFMAs (304 instead of 960 LDS reads per tile at four phases).
- *   Same products, another fp32 summation order: agrees with bit 4 off to accumulation rounding (not bit-identical).  Measured at
- *   32 x 131072, same box, d = 4 ... 2048: 1.40 ms per launch against 1.46 (profiles/r04_tcn_forms_reuse.log).
- * bit 5 (bf16 mode, with form 2 and bit 4; default 1 since round 5): block 0 (2 -> 128 channels) is not launched - the loader waves of the d = 2 block's
- *   duo kernel compute its outputs straight into the LDS image (same arithmetic as tcn_block0_mfma_kernel: bit-identical results, checked
- *   on the MI355X at 32 x 131072; no 1.07 GB store and re-read).  Measured, same box, alternating (profiles/r04_tcn_forms_fuse0.log):
- *   the fused launch 1.58 ms against 0.31 + 1.44 for the two kernels, -0.2 ms per forward (1 % of the step).  Applies only when block 1 is
- *   the d = 2 block on two-phase class-major tiles (>= 128 steps per phase) and is not the last block; otherwise the separate block-0
- *   kernel runs - mst_tcn_get_tuning reports which happened.  Emulator tests (bit identity over random shapes) + tests/test_gpu_parity.py form 53.
- * bit 6 (bf16x3 mode; default 1 since round 5): the eight-phase half-tile kernel (d >= 4096 at L = 131072: 2 of that mode's 13 launches) runs a
- *   class-major loop too (pseudo-classes of two taps of one parity); results agree with bit 6 off to accumulation rounding (GPU test:
- *   <= 1e-5 on the waveform, both within 1e-4 of the oracle).  Measured, same box, alternating: 571.7 / 572.1 against 566.2 segments/s for the
- *   whole bf16x3 step at 32 x 131072 (profiles/r05_x3_ab_bit6_53_117.jsonl).
- * bit 7 (bf16 mode, with form 2 and bit 4; default 1 since round 6): the two- and four-phase blocks (d = 2 ... 2048 at L = 131072: 11 of the 13 dense launches)
- *   run tcn_block_bf16_kernel<P, false, 8, 2> - ONE 256-time tile per workgroup of four waves, TWO workgroups per CU, the duo kernel's
- *   class-major loop (same products, same order: bit-identical to bit 7 off) - instead of the persistent duo kernel: two matrix waves per SIMD
- *   cover each other's staging and epilogue.  With bit 5 the d = 2 block's workgroups compute block 0 in their staging phase (<2, false, 8, 2, true>:
- *   the duo loader's arithmetic, bit for bit).  Same box, alternating (profiles/r06_tcn_forms_onetile_ab.txt, r06_tcn_forms_onetile_fuse0_ab.txt):
- *   1.312-1.318 ms per launch against 1.404-1.409 for the duo kernel, the d = 2 launch with block 0 inside 1.47 against 1.56 (a 128-time form at
- *   three workgroups per CU: 1.336-1.338 - it streams every weight fragment twice as often, and under the chip's power limit a tile's energy is
- *   what counts; EXPERIMENTS.md E.6).  One case is NOT bit-identical to bit 7 off: a LAST block with two / four phases (segments of >= 2^19 samples: d = 8192
- *   has 64 steps per phase) carries the fused output head and ran the one-tile kernel's tap-major loop; with bit 7 it runs the class-major loop
- *   (<4, true, 8, 2>: 1.32 against 1.36 ms) - its activation differs by fp32 summation order, the waveform by <= 2e-3 after the bf16 re-rounding
- *   (profiles/r06_tcn_forms_2p19_segments.txt; both within the bf16 tolerance of the oracle and of the reference's real-audio goldens).
- *   Bit 7 also selects, for a block whose phase sequences are EXACTLY one 256-time tile (L = 64 d, 32 d or 16 d: d = 2048 / 4096 / 8192 at L = 131072), the
- *   unrolled forms <4 | 8 | 16, ., 8, 1>: no all-padding (column tile, tap) pair exists, the LDS image keeps only the halo steps a row window can straddle
- *   into (280 / 272 / 256 rows), the sixteen-phase form carries the fused head.  The four-phase form sums in the duo kernel's order (bit-identical); the
- *   other two in another fp32 order than round 5's 128-time forms (one bf16 ulp on the activation).  1.32 -> 1.26, 1.25 -> 1.19, 1.21 -> 1.03 ms
- *   (profiles/r06_tcn_whole_sequence_256_tiles_ab.txt). */
+/* tuning flags of the handle (the table above; default 245 = bits 0, 2, 4, 5, 6, 7), in detail:
+ *   bf16 form 2: the two- and four-phase blocks that are not the last one run tcn_block_bf16_kernel<P, false, 8, 2> (one 256-time tile per
+ *     workgroup, two workgroups per CU, B fragments reused across the taps of a class); every other block - P = 1 (odd dilations), the 128-time
+ *     and sixteen-phase tilings - runs what form 0 runs, bit 7's forms aside.  The two forms agree to fp32 accumulation rounding.
+ *   bit 5: applies only when block 1 is the d = 2 block on two-phase tiles (>= 128 steps per phase) and not the last block; otherwise the
+ *     separate block-0 kernel runs - mst_tcn_get_tuning reports which happened.  Same bits either way.
+ *   bit 7: a block whose phase sequences are EXACTLY one 256-time tile (L = 64 d, 32 d or 16 d: d = 2048 / 4096 / 8192 at L = 131072) runs the
+ *     unrolled forms <4 | 8 | 16, ., 8, 1> (no all-padding (column tile, tap) pair; the sixteen-phase form carries the fused head): the
+ *     four-phase form is bit-identical to bit 7 off, the other two one bf16 ulp away on the activation.  A four-phase LAST block (segments of
+ *     >= 2^19 samples) runs the class-major head <4, true, 8, 2> instead of the tap-major <4, true, 8>: the waveform moves by <= 2e-3 (a
+ *     two-phase last block is tap-major either way).
+ * Measurements behind the defaults: EXPERIMENTS.md and profiles/.  mst_tcn_get_tuning returns the flags as set. */
 int mst_tcn_set_tuning(MstTcn *tcn, int flags);
 /* the flags in force and whether the handle's LAST forward ran block 0 inside block 1's launch (bit 5 is a request: see its conditions above);
  * either pointer may be null. */
@@ -233,9 +202,8 @@ int mst_enc_load_conv(MstEnc *enc, int block, int which, const float *w, const f
 int mst_enc_set_tuning(MstEnc *enc, long rows_min_tiles);
 /* workgroup order of the channel-minor conv kernel (bf16 / bf16x3 modes).  bit 0 (default on): layers with more weight bytes than
  * activation bytes run their workgroups in weight-major order - all column tiles of one (channel tile, k-slice) on one XCD, so a
- * weight slice crosses the fabric once instead of once per XCD.  bit 1 (default off: measured 7-12 % slower): the 128-channel x
- * 128-column tile with its waves 2 x 2 (enc_conv_nlc22_kernel: two MFMAs per LDS read, every weight fragment fetched by two waves).
- * bit 2 (exact-fp32 mode, a test hook): gather through 64-bit addresses - the path that activations beyond the 32-bit offset range take
+ * weight slice crosses the fabric once instead of once per XCD.  bit 1: rejected (MST_ERR_ARG; it selected a 2 x 2 wave
+ * tiling of the 128-channel kernel, measured 7-12 % slower).  bit 2 (exact-fp32 mode, a test hook): gather through 64-bit addresses - the path that activations beyond the 32-bit offset range take
  * by themselves - instead of buffer loads.  Same bits either way.  (Round 5 built and measured an in-kernel split-K finalize - tickets, last
  * workgroup of a tile sums the partial tiles - as bit 3: correct, and 5 x SLOWER per layer (the device-scope release fence writes the
  * whole L2 back on this part; EXPERIMENTS.md D.3): not in the library.)

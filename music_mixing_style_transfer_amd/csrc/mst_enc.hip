@@ -93,7 +93,7 @@ int tcn_launch_generic(const MstEncConv &c, const float *x, float *y, int B, int
 struct MstEnc {
     MstEncDesc d;
     std::vector<MstEncConv> conv;   // 2 per block
-    int schedule = 1;               // bit 5: the 128-channel layers on the four-wave im2col kernel instead of the raw-rows kernel with loader waves; bit 4: blocks 1 / 2 (bf16 mode) as two launches each instead of the fused kernel; bit 3: the stereo block as two direct-kernel launches instead of the fused kernel (the bit-identical reference form); bit 1: 2 x 2 wave tiling of the 128-channel conv kernel (measured slower: off); bit 0: weight-major workgroup order for the weight-heavy layers (mst_enc_set_schedule)
+    int schedule = 1;               // bit 5: the 128-channel layers on the four-wave im2col kernel instead of the raw-rows kernel with loader waves; bit 4: blocks 1 / 2 (bf16 mode) as two launches each instead of the fused kernel; bit 3: the stereo block as two direct-kernel launches instead of the fused kernel (the bit-identical reference form); bit 0: weight-major workgroup order for the weight-heavy layers (mst_enc_set_schedule)
     void *zeros = nullptr;          // 256 bytes of zeros: what the channel-minor conv kernel fetches for rows / k-slots outside the problem
     long rows_min_tiles = 512;      // bf16 mode: layers with at least this many tiles keep their input rows resident in LDS (mst_enc_set_tuning)
 };
@@ -281,7 +281,8 @@ extern "C" int mst_enc_zero_stuff(const float *x, float *y, long rows, long L, i
 }
 
 extern "C" int mst_enc_set_schedule(MstEnc *e, int flags) {
-    if (!e || flags < 0 || flags > 63) return fail(MST_ERR_ARG, "mst_enc_set_schedule: flags 0..63");
+    if (!e || flags < 0 || flags > 63 || (flags & 2))
+        return fail(MST_ERR_ARG, "mst_enc_set_schedule: flags 0..63 without bit 1 (the 2 x 2 wave tiling left the library)");
     e->schedule = flags;
     return MST_OK;
 }
@@ -619,7 +620,7 @@ int enc_launch_nlc(const MstEncConv &c, const __bf16 *x, __bf16 *y, float *scrat
             return MST_OK;
         }
     }
-    if (!x3 && !(schedule & 2) && !(schedule & 32) && enc_taps_fits(c, Lout) && a.Ntot < 0x7fffff00L && (!residual || (Lin == Lout && c.cin == c.cout))) {          // the 128-channel layers on raw input rows with loader waves
+    if (!x3 && !(schedule & 32) && enc_taps_fits(c, Lout) && a.Ntot < 0x7fffff00L && (!residual || (Lin == Lout && c.cin == c.cout))) {          // the 128-channel layers on raw input rows with loader waves
         EncTapsArgs t;
         t.x = x;
         t.y = y;
@@ -664,24 +665,17 @@ int enc_launch_nlc(const MstEncConv &c, const __bf16 *x, __bf16 *y, float *scrat
         a.wmajor = (int)cotiles;
         grid = dim3((unsigned)(ntiles * cotiles * a.S));
     }
-    const bool w22 = c.mw == 4 && (schedule & 2);          // the 128 x 128 tile with its waves 2 x 2 (two MFMAs per LDS read)
     if (x3) {
         switch (c.mw) {
             case 1: MST_LAUNCH((enc_conv_nlc_kernel<1, true>), grid, dim3(256), stream, a); break;
             case 2: MST_LAUNCH((enc_conv_nlc_kernel<2, true>), grid, dim3(256), stream, a); break;
-            default:
-                if (w22) MST_LAUNCH((enc_conv_nlc22_kernel<true>), grid, dim3(256), stream, a);
-                else MST_LAUNCH((enc_conv_nlc_kernel<4, true>), grid, dim3(256), stream, a);
-                break;
+            default: MST_LAUNCH((enc_conv_nlc_kernel<4, true>), grid, dim3(256), stream, a); break;
         }
     } else
     switch (c.mw) {
         case 1: MST_LAUNCH((enc_conv_nlc_kernel<1>), grid, dim3(256), stream, a); break;
         case 2: MST_LAUNCH((enc_conv_nlc_kernel<2>), grid, dim3(256), stream, a); break;
-        default:
-            if (w22) MST_LAUNCH((enc_conv_nlc22_kernel<false>), grid, dim3(256), stream, a);
-            else MST_LAUNCH((enc_conv_nlc_kernel<4>), grid, dim3(256), stream, a);
-            break;
+        default: MST_LAUNCH((enc_conv_nlc_kernel<4>), grid, dim3(256), stream, a); break;
     }
     MST_CHECK_LAUNCH("enc_conv_nlc_kernel");
     if (a.S > 1) {

@@ -29,16 +29,15 @@ struct MstTcn {
     float *out_w = nullptr, *out_b = nullptr;
     bool out_loaded = false;
     void *zero_row = nullptr;     // 1 KB of zeros: what the block kernels stage for time steps outside the segment
-    int x3_small_tiles = 1;       // bf16x3 mode: 128-time tiles of <= 2 phases, two workgroups per CU (mst_tcn_set_tuning; measured 5.13 vs 5.45 ms)
-    int x3_half_cm = 1;           // bf16x3 mode: class-major loop in the eight-phase half-tile kernel (mst_tcn_set_tuning bit 6; round 5: GPU-tested,
-                                  // 566 -> 572 segments/s at 32 x 131072, profiles/r05_x3_ab_bit6_53_117.jsonl: on)
-    int bf16_fuse0 = 1;           // bf16 mode: block 0 computed by the loader waves of block 1's duo kernel (mst_tcn_set_tuning bit 5; measured -0.2 ms
-                                  // per forward, bit-identical to the separate kernel; default since round 5 - tests/test_gpu_parity.py form 53)
+    // kernel forms: the mst_tcn_set_tuning flags as set (include/mst_hip.h; measured at 32 x 131072: bit 0 5.13 against 5.45 ms per bf16x3 launch,
+    // bit 5 -0.2 ms per bf16 forward, bit 6 572 against 566 bf16x3 segments/s - profiles/r05_x3_ab_bit6_53_117.jsonl)
+    int tuning = 245;
+    bool x3_small_tiles() const { return tuning & 1; }              // bf16x3: 128-time tiles of <= 2 phases, two workgroups per CU
+    bool bf16_cm() const { return ((tuning >> 1) & 3) == 2; }       // bf16 form 2: two- / four-phase blocks on class-major 256-time tiles
+    bool bf16_fuse0() const { return bf16_cm() && (tuning & 32); }  // bf16: block 0 inside the d = 2 block's launch
+    bool x3_half_cm() const { return tuning & 64; }                 // bf16x3: class-major loop in the eight-phase half-tile kernel
+    bool bf16_whole() const { return bf16_cm() && (tuning & 128); } // bf16: whole-sequence 256-time tiles, class-major head of a four-phase last block
     int last_fused0 = 0;          // whether the last forward of this handle really ran block 0 inside block 1's launch (mst_tcn_get_tuning)
-    int bf16_reuse = 1;           // bf16 mode, duo kernel: the class-major main loop (mst_tcn_set_tuning bit 4; measured 1.40 vs 1.46 ms per launch)
-    int bf16_form = 2;            // bf16 mode, form of the block kernel (mst_tcn_set_tuning bits 1-2): 0 one tile per workgroup, 2 duo (default)
-    int bf16_onetile = 1;         // bf16 mode: the two- / four-phase class-major blocks on the ONE-TILE kernel's 256-time tiles, two workgroups per CU, instead of the duo
-                                  // kernel (mst_tcn_set_tuning bit 7, round 6: 1.31 against 1.40 ms per launch, the d = 2 block with block 0 inside 1.47 against 1.56; bit-identical)
     std::vector<hipEvent_t> ev;   // timing hook: (nblocks + 2) events per recorded forward
     int ev_max = 0, ev_used = 0;
 };
@@ -289,45 +288,11 @@ int choose_phases(int d, int L, int precision) {
     return P;
 }
 
-// the persistent double-tile bf16 kernel: one workgroup per CU
-template <int P, int NQ> int launch_block_duo(TcnBlockArgs a, void *stream, int reuse = 0) {
-    if (a.x0 && !(P == 2 && NQ == 8 && reuse)) return fail(MST_ERR_STATE, "tcn_block_bf16_duo_kernel: block 0 can only be fused into two-phase class-major tiles");
-    const long nsteps = ((long)a.L + a.d - 1) / a.d;
-    a.tiles_step = (int)((nsteps + (32 * NQ) / P - 1) / ((32 * NQ) / P));
-    const long ntiles = (long)a.B * a.tiles_phase * a.tiles_step;
-    if (ntiles > 0x7fffffffL) return fail(MST_ERR_ARG, "tcn_block_bf16_duo_kernel: more than 2^31 tiles");
-    long grid = mst_num_cus();
-    if (grid > ntiles) grid = ntiles;
-    a.xcd_tiles = 0;
-    if (grid >= 8) {
-        grid -= grid % 8;
-        a.xcd_tiles = (int)((ntiles + 7) / 8);
-    }
-    if constexpr (P == 2 && NQ == 8) {
-        if (reuse && a.x0) {          // block 0 computed by the loader waves (mst_tcn_set_tuning bit 5)
-            MST_LAUNCH((tcn_block_bf16_duo_kernel<P, false, NQ, true, true>), dim3((unsigned)grid), dim3(512), stream, a);
-            MST_CHECK_LAUNCH("tcn_block_bf16_duo_kernel");
-            return MST_OK;
-        }
-    }
-    if constexpr ((P == 4 || P == 2) && NQ == 8) {
-        if (reuse) {          // the class-major main loop (B fragments reused across the taps of a class)
-            MST_LAUNCH((tcn_block_bf16_duo_kernel<P, false, NQ, true>), dim3((unsigned)grid), dim3(512), stream, a);
-            MST_CHECK_LAUNCH("tcn_block_bf16_duo_kernel");
-            return MST_OK;
-        }
-    }
-    MST_LAUNCH((tcn_block_bf16_duo_kernel<P, false, NQ>), dim3((unsigned)grid), dim3(512), stream, a);
-    MST_CHECK_LAUNCH("tcn_block_bf16_duo_kernel");
-    return MST_OK;
-}
-
-template <int P> int launch_block(int precision, const TcnBlockArgs &a0, int grid, void *stream, int x3_small = 0, int bf16_form = 0,
-                                  int bf16_tile = TILE_DEFAULT, int bf16_reuse = 0, int x3_half_cm = 0, int bf16_onetile = 0) {
+template <int P> int launch_block(const MstTcn &t, int precision, const TcnBlockArgs &a0, int grid, void *stream, int x3_small, int bf16_tile) {
     TcnBlockArgs a = a0;
     if constexpr (P == 4) {
-        // (the same 128-time form for EVERY block - three workgroups per CU instead of the duo kernel - measured 1.53-1.58 ms per launch
-        //  against 1.48-1.53: it only wins where the eight-phase tiles' halo is the alternative)
+        // (the same 128-time form for EVERY block - three workgroups per CU - measured 1.53-1.58 ms per launch against 1.48-1.53 for round 3's
+        //  persistent 256-time kernel: it only wins where the eight-phase tiles' halo is the alternative)
         if (precision == MST_PREC_BF16 && bf16_tile == TILE_128_FOUR_PHASES) {          // 128-time tiles of 4 phases (one-tile kernel, three workgroups per CU)
             const long nsteps = ((long)a.L + a.d - 1) / a.d;
             a.tiles_step = (int)((nsteps + 128 / P - 1) / (128 / P));
@@ -362,32 +327,26 @@ template <int P> int launch_block(int precision, const TcnBlockArgs &a0, int gri
             return MST_OK;
         }
     }
-    if (precision == MST_PREC_BF16 && bf16_form == 2) {
-        // 256-time tiles only: at P = 8 (128-time tiles: half the work per tile for the same two barriers) the duo form measured
-        // 1.62-1.82 ms against 1.50 ms, those blocks run the one-tile-per-workgroup kernel
-        // (the last block - fused output head, 32 more live registers - spills in the duo form and runs the one-tile kernel too)
+    if (precision == MST_PREC_BF16 && t.bf16_cm()) {
+        // form 2: the two- and four-phase blocks on 256-time class-major tiles, two workgroups per CU (round 6: 1.31 ms per launch against 1.40
+        // for round 3's persistent kernel with the same loop); P = 1 and the eight-phase blocks run the general forms below
         if constexpr (P == 4) {
-            // bit 7 (round 6): the class-major four-phase blocks on the one-tile kernel, 256-time tiles, two workgroups per CU
-            if (bf16_onetile && bf16_reuse) {
+            if (!a.y_out || t.bf16_whole()) {          // the last block of a long segment (fused head): class-major with bit 7, else tap-major below
                 if (grid % 8 == 0) a.xcd_tiles = grid / 8;
-                if (a.y_out) MST_LAUNCH((tcn_block_bf16_kernel<P, true, 8, 2>), dim3(grid), dim3(256), stream, a);          // the last block of a long segment: fused head
+                if (a.y_out) MST_LAUNCH((tcn_block_bf16_kernel<P, true, 8, 2>), dim3(grid), dim3(256), stream, a);
                 else MST_LAUNCH((tcn_block_bf16_kernel<P, false, 8, 2>), dim3(grid), dim3(256), stream, a);
                 MST_CHECK_LAUNCH("tcn_block_bf16_kernel");
                 return MST_OK;
             }
         }
         if constexpr (P == 2) {
-            // ... and the two-phase blocks (the d = 2 block; with bit 5 block 0 is computed in its staging)
-            if (!a.y_out && bf16_onetile && bf16_reuse) {
+            if (!a.y_out) {          // the d = 2 block; with bit 5 it computes block 0 in its staging (a two-phase last block runs tap-major below)
                 if (grid % 8 == 0) a.xcd_tiles = grid / 8;
                 if (a.x0) MST_LAUNCH((tcn_block_bf16_kernel<P, false, 8, 2, true>), dim3(grid), dim3(256), stream, a);
                 else MST_LAUNCH((tcn_block_bf16_kernel<P, false, 8, 2>), dim3(grid), dim3(256), stream, a);
                 MST_CHECK_LAUNCH("tcn_block_bf16_kernel");
                 return MST_OK;
             }
-        }
-        if constexpr (P <= 4) {
-            if (!a.y_out) return launch_block_duo<P, 8>(a, stream, bf16_reuse);
         }
     }
     if (precision == MST_PREC_BF16X3) {
@@ -409,7 +368,7 @@ template <int P> int launch_block(int precision, const TcnBlockArgs &a0, int gri
             const long g2 = (long)a.B * a.tiles_phase * a.tiles_step;
             if (g2 % 8 == 0) a.xcd_tiles = (int)(g2 / 8);
             if constexpr (P == 8) {    // 8-phase tiles: the input staged in two halves of 64 channels (60 KB of LDS, two workgroups per CU)
-                if (x3_half_cm)
+                if (t.x3_half_cm())
                     MST_LAUNCH((tcn_block_bf16x3_half_kernel<P, NQ, true>), dim3((unsigned)g2), dim3(256), stream, a);
                 else
                     MST_LAUNCH((tcn_block_bf16x3_half_kernel<P, NQ>), dim3((unsigned)g2), dim3(256), stream, a);
@@ -499,9 +458,9 @@ int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, i
         MST_HIP_TRY(hipEventRecord(ev[0], (hipStream_t)stream));
     }
 
-    // block 0 inside block 1's launch (bf16, tuning bit 5): block 1 must be the d = 2 block on two-phase class-major tiles (the one-tile kernel
-    // with bit 7, else the duo kernel) and not the last block; the probes of block 0 itself (n_run == 1) always run the separate kernel
-    const bool fuse0 = precision == MST_PREC_BF16 && t->bf16_fuse0 && t->bf16_reuse && t->bf16_form == 2 && t->blk[0].w_bf16 && n_run >= 2 &&
+    // block 0 inside block 1's launch (bf16, tuning bit 5): block 1 must be the d = 2 block on two-phase class-major tiles (form 2) and not
+    // the last block; the probes of block 0 itself (n_run == 1) always run the separate kernel
+    const bool fuse0 = precision == MST_PREC_BF16 && t->bf16_fuse0() && t->blk[0].w_bf16 && n_run >= 2 &&
                        t->d.nblocks > 2 && t->d.dilations[0] == 1 && t->d.dilations[1] == 2 && choose_phases(2, L, precision) == 2;
     t->last_fused0 = fuse0 ? 1 : 0;
     if (fuse0) {
@@ -533,8 +492,8 @@ int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, i
     bool fused_head = false;
     for (int n = 1; n < n_run; ++n) {
         const int d = t->d.dilations[n];
-        int P = choose_phases(d, L, (precision == MST_PREC_BF16X3 && t->x3_small_tiles) ? MST_PREC_BF16X3 + 100 : precision);
-        const int x3_small = (precision == MST_PREC_BF16X3 && t->x3_small_tiles && P <= 2) ? 1 : 0;
+        int P = choose_phases(d, L, (precision == MST_PREC_BF16X3 && t->x3_small_tiles()) ? MST_PREC_BF16X3 + 100 : precision);
+        const int x3_small = (precision == MST_PREC_BF16X3 && t->x3_small_tiles() && P <= 2) ? 1 : 0;
         // bf16, 17 ... 32 steps per phase (d = 4096 at L = 131072): 128-time tiles of FOUR phases x 32 steps (184 rows staged per 128
         // outputs, three workgroups per CU) instead of eight phases x 16 steps (240 rows, two workgroups per CU)
         int bf16_tile = TILE_DEFAULT;
@@ -548,7 +507,7 @@ int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, i
         // bf16 (tuning bit 7), a block whose phase sequences are EXACTLY one 256-time tile - sixteen phases x 16 steps (d = 8192 at L = 131072, the last
         // block), eight x 32 (d = 4096), four x 64 (d = 2048): the unrolled class-major loop without the all-padding (column tile, tap) pairs, an LDS image
         // without the halo steps no live row window reaches (256 / 272 / 280 rows), two workgroups per CU
-        if (precision == MST_PREC_BF16 && t->bf16_onetile && t->bf16_reuse && t->bf16_form == 2) {
+        if (precision == MST_PREC_BF16 && t->bf16_whole()) {
             const long ns = ((long)L + d - 1) / d;
             const int Pw = ns == 16 ? 16 : (ns == 32 ? 8 : (ns == 64 ? 4 : 0));
             // (with the fused output head - the last block - only the sixteen-phase form fits 256 registers: 248; the other two would spill)
@@ -595,11 +554,11 @@ int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, i
         if (grid > 0x7fffffffL) return fail(MST_ERR_ARG, "mst_tcn_forward: grid too large");
         int rc;
         switch (P) {
-            case 1: rc = launch_block<1>(precision, a, (int)grid, stream, x3_small, t->bf16_form, bf16_tile, t->bf16_reuse, t->x3_half_cm, t->bf16_onetile); break;
-            case 2: rc = launch_block<2>(precision, a, (int)grid, stream, x3_small, t->bf16_form, bf16_tile, t->bf16_reuse, t->x3_half_cm, t->bf16_onetile); break;
-            case 4: rc = launch_block<4>(precision, a, (int)grid, stream, x3_small, t->bf16_form, bf16_tile, t->bf16_reuse, t->x3_half_cm, t->bf16_onetile); break;
-            case 8: rc = launch_block<8>(precision, a, (int)grid, stream, x3_small, t->bf16_form, bf16_tile, t->bf16_reuse, t->x3_half_cm, t->bf16_onetile); break;
-            default: rc = launch_block<16>(precision, a, (int)grid, stream, 0, t->bf16_form, bf16_tile); break;
+            case 1: rc = launch_block<1>(*t, precision, a, (int)grid, stream, x3_small, bf16_tile); break;
+            case 2: rc = launch_block<2>(*t, precision, a, (int)grid, stream, x3_small, bf16_tile); break;
+            case 4: rc = launch_block<4>(*t, precision, a, (int)grid, stream, x3_small, bf16_tile); break;
+            case 8: rc = launch_block<8>(*t, precision, a, (int)grid, stream, x3_small, bf16_tile); break;
+            default: rc = launch_block<16>(*t, precision, a, (int)grid, stream, 0, bf16_tile); break;
         }
         if (rc) return rc;
         if (ev) MST_HIP_TRY(hipEventRecord(ev[n + 1], (hipStream_t)stream));
@@ -644,21 +603,17 @@ int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, i
 
 extern "C" int mst_tcn_set_tuning(MstTcn *t, int flags) {
     if (!t) return fail(MST_ERR_ARG, "mst_tcn_set_tuning: null handle");
-    if (flags < 0 || flags > 255 || (((flags >> 1) & 3) != 0 && ((flags >> 1) & 3) != 2) || ((flags >> 3) & 1))
-        return fail(MST_ERR_ARG, "mst_tcn_set_tuning: unknown flag bits (form 1 - the stream kernel - and bit 3 - the split-bf16 duo kernel - left the library in round 5)");
-    t->x3_small_tiles = flags & 1;
-    t->bf16_form = (flags >> 1) & 3;
-    t->bf16_reuse = (flags >> 4) & 1;
-    t->bf16_fuse0 = (flags >> 5) & 1;
-    t->x3_half_cm = (flags >> 6) & 1;
-    t->bf16_onetile = (flags >> 7) & 1;
+    const int form = (flags >> 1) & 3;
+    if (flags < 0 || flags > 255 || (form != 0 && form != 2) || ((flags >> 3) & 1) || (form == 2 && !((flags >> 4) & 1)))
+        return fail(MST_ERR_ARG, "mst_tcn_set_tuning: unknown flag bits (bits 1-2 = 0 or 2, form 2 with bit 4, no bit 3: the kernels the others "
+                                 "selected left the library)");
+    t->tuning = flags;
     return MST_OK;
 }
 
 extern "C" int mst_tcn_get_tuning(const MstTcn *t, int *flags, int *last_forward_fused_block0) {
     if (!t) return fail(MST_ERR_ARG, "mst_tcn_get_tuning: null handle");
-    if (flags)
-        *flags = t->x3_small_tiles | t->bf16_form << 1 | t->bf16_reuse << 4 | t->bf16_fuse0 << 5 | t->x3_half_cm << 6 | t->bf16_onetile << 7;
+    if (flags) *flags = t->tuning;
     if (last_forward_fused_block0) *last_forward_fused_block0 = t->last_fused0;
     return MST_OK;
 }

@@ -44,15 +44,15 @@ struct TcnBlockArgs {
     const void *zeros;    // >= 256 bytes of zeros in device memory: the row staged for time steps outside the segment
     int xcd_tiles;        // > 0: tiles per XCD; workgroup i (dispatched to XCD i % 8) takes tile (i % 8) * xcd_tiles + i / 8, so that
                           // neighbouring time tiles (which share their halo rows) run on the same XCD and meet in its L2
-    // block 0 fused into this launch (duo kernel with FUSE0, d = P = 2: a tile's rows are consecutive samples): the loader waves compute
-    // the tile's input rows from the waveform with block 0's weights instead of fetching them (x is not read)
+    // block 0 fused into this launch (tcn_block_bf16_kernel with FUSE0, d = P = 2: a tile's rows are consecutive samples): the workgroup
+    // computes the tile's input rows from the waveform with block 0's weights instead of fetching them (x is not read)
     const float *x0 = nullptr;         // waveform [B][2][L]
     const void *w0pk = nullptr;        // block 0's A fragments (TcnBlock0Args::wpk16)
     const float *shift0 = nullptr, *film0 = nullptr, *res0 = nullptr;      // block 0's BN shift, FiLM rows (film_rows of them), residual scale
 };
 
 // ------------------------------------------------------------------------------------------------
-// Block 0's arithmetic in the bf16 mode, shared by tcn_block0_mfma_kernel and the duo kernel's FUSE0 loader so that both produce the same
+// Block 0's arithmetic in the bf16 mode, shared by tcn_block0_mfma_kernel and tcn_block_bf16_kernel's FUSE0 staging so that both produce the same
 // bits: the B fragments of one k-step (16 of the 32 k = ci * 15 + j; k >= 30 is padding) for the 32 output times o0 .. o0 + 31 of a
 // waveform window xs[ci][k] = x[ci][t_first - 7 + k], split hi + lo; and one output element.
 // ------------------------------------------------------------------------------------------------
@@ -184,8 +184,8 @@ __device__ __forceinline__ void tcn_class_major_whole_tile(f32x4 (&acc)[2][NC], 
 // B fragment feeds two MFMAs) - and under the chip's power limit it runs 15 % faster: on realistic operands the bare instruction
 // stream sustains 1934-1982 TFLOP/s against 1666-1685, the whole main loop 1570-1585 against 1367-1377
 // (tools/micro/tcn_mainloop_variants.hip, profiles/archive/r02_micro_tcn_mainloop_variants_16x16.txt).
-// The tap-major loop below serves the tiles that do not span their phase sequence; whole-sequence 128-time tiles run
-// tcn_class_major_whole_tile, the duo kernel's 256-time tiles tcn_reuse_class (B fragments reused across taps).
+// The tap-major loop below serves the tiles that do not span their phase sequence; whole-sequence tiles run
+// tcn_class_major_whole_tile, the class-major 256-time tiles of two / four phases tcn_reuse_class (B fragments reused across taps).
 // TCN_LIVE_MIN_P: phases per tile from which all-padding (column tile, tap) pairs are skipped under a branch.  8 was measured and dropped for this kernel (round 4, same-box
 // A/B at 32 x 131072): the d = 4096 / 8192 blocks skip 10 % / 20 % of their MFMAs but run 1.58 -> 1.85 / 1.57 -> 1.74 ms - the wave-uniform
 // branches around the MFMA pairs break the (mfma, mfma, ds_read) software pipeline; the split-bf16 kernel (6 MFMAs per branch) gains 3-5 %
@@ -194,19 +194,19 @@ constexpr int TCN_LIVE_MIN_P = 16;
 // kernel holds ONLY the unrolled class-major loop.  With both loops in one kernel (chosen per workgroup) the register allocation was the
 // maximum over the two and <4, false, 4> spilled 10 VGPRs at three workgroups per CU (44 bytes of scratch per lane); split, neither form spills.
 // WHOLE: 0 tap-major loop; 1 every tile spans its whole phase sequence (128-time tiles, dead pairs left out);
-// 2 (round 6, mst_tcn_set_tuning bit 7): 256-time tiles of two / four phases with the duo kernel's class-major loop (tcn_reuse_class: the duo
-// kernel's products in the duo kernel's order - bit-identical to it), two workgroups per CU = two matrix waves per SIMD whose staging and
-// epilogue hide behind each other's main loops.  Same-box alternating A/B at 32 x 131072, d = 4 ... 2048 (profiles/r06_tcn_forms_onetile_ab.txt):
-// duo kernel 1.404-1.409 ms per launch, 128-time class-major tiles at three workgroups per CU 1.336-1.338, this form 1.312-1.318.  The
+// 2 (round 6, mst_tcn_set_tuning form 2): 256-time tiles of two / four phases with the class-major loop (tcn_reuse_class), two workgroups per
+// CU = two matrix waves per SIMD whose staging and epilogue hide behind each other's main loops.  Same-box alternating A/B at 32 x 131072,
+// d = 4 ... 2048 (profiles/r06_tcn_forms_onetile_ab.txt): this form 1.312-1.318 ms per launch, 128-time class-major tiles at three workgroups
+// per CU 1.336-1.338, round 3's persistent double-tile kernel (one workgroup per CU, removed since) with the same loop 1.404-1.409.  The
 // three-workgroup form keeps the matrix pipe busy 0.94 of the kernel's cycles (profiles/r06_pmc_sq_tcn_block_bf16_cm128.txt) but pulls the
 // shader clock to ~1.55-1.7 GHz under the chip's power limit: what a tile costs in ENERGY decides, and 256-time tiles stream every weight
 // fragment from L2 half as often (8 GB per launch instead of 16) and stage 1.22 instead of 1.44 rows per output row.
-template <int P, int NU, bool LAST, int NUMAX, bool WRAP = true>
+template <int P, int NU, bool LAST, int NUMAX>
 __device__ __forceinline__ void tcn_reuse_class(f32x4 (&acc)[2][16], bf16x8 (&A0)[NUMAX][2], bf16x8 (&A1)[NUMAX][2], bf16x8 (&ring)[4],
                                                 const unsigned char *sm, const MstStream16 &wst, unsigned aoff, int c, int cn, int l16, int g);
 // FUSE0 (round 6; two-phase class-major tiles, d = 2: a tile's rows are consecutive samples): block 0 is not launched - the workgroup computes
-// its tile's input rows from the waveform with tcn_block0_mfma_kernel's arithmetic (the duo kernel's FUSE0 loader, same fragments, same MFMA
-// order, same epilogue function: the same bits) instead of fetching them; the other workgroup of the CU runs its main loop meanwhile.
+// its tile's input rows from the waveform with tcn_block0_mfma_kernel's arithmetic (same fragments, same MFMA order, same epilogue function:
+// the same bits) instead of fetching them; the other workgroup of the CU runs its main loop meanwhile.
 template <int P, bool FUSE_OUT, int NQ, int WHOLE = 0, bool FUSE0 = false>
 __global__ __launch_bounds__(256, (NQ == 4 ? (P <= 4 ? 3 : 2) : (P <= 4 || WHOLE == 1 ? 2 : 1))) void tcn_block_bf16_kernel(TcnBlockArgs a) {
     static_assert(WHOLE != 1 || ((P == 8 || P == 4) && NQ == 4) || ((P == 16 || P == 8 || P == 4) && NQ == 8),
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(256, (NQ == 4 ? (P <= 4 ? 3 : 2) : (P <= 4 || WHOLE
             }
 #pragma unroll 1
             for (int c = 0; c < NCLS - 1; ++c) tcn_reuse_class<P, NUMAX, false, NUMAX>(acc, A0, A1, ring, smem, wst, aoff, c, c + 1, l16, g);
-            tcn_reuse_class<P, 15 / NCLS, true, NUMAX, false>(acc, A0, A1, ring, smem, wst, aoff, NCLS - 1, 0, l16, g);
+            tcn_reuse_class<P, 15 / NCLS, true, NUMAX>(acc, A0, A1, ring, smem, wst, aoff, NCLS - 1, 0, l16, g);
         } else tap_major();
     }
 
@@ -534,7 +534,7 @@ __global__ __launch_bounds__(256, (NQ == 4 ? (P <= 4 ? 3 : 2) : (P <= 4 || WHOLE
 }
 
 // ------------------------------------------------------------------------------------------------
-// Main loop of the 256-time tile with B-FRAGMENT REUSE ACROSS TAPS (round 4, REUSE form of the duo kernel).  With P phases per tile the
+// Main loop of the 256-time tile with B-FRAGMENT REUSE ACROSS TAPS (round 4; tcn_block_bf16_kernel<P, ., 8, 2>, tcn_calib_mainloop_kernel).  With P phases per tile the
 // B fragment of (tap j, column tile q) is rows P j + 16 q .. + 15 of the LDS image - the same rows as (tap j + 16 / P, column tile q - 1):
 // at P = 4 the tap-major loop reads each of the 75 x 4 distinct fragments up to four times (960 ds_read_b128 per tile and wave, one per
 // MFMA pair).  Class-major order: taps fall into NCLS = 16 / P classes c = j mod NCLS; for one class and one k-step kk the wave holds the
@@ -543,13 +543,12 @@ __global__ __launch_bounds__(256, (NQ == 4 ? (P <= 4 ? 3 : 2) : (P <= 4 || WHOLE
 // 960, up to eight MFMAs per read (P = 2: 544, up to four), the weight stream unchanged (128 fragments per tile against 120).  Same
 // products, summed class by class instead of tap by tap (fp32 accumulation: results differ from the tap-major loop by rounding only).
 // Measured, same box: the bare main loop on realistic operands 1.145 ms against 1.230 (tools/micro/tcn_mainloop_variants.hip reuse16x16 /
-// base16x16, profiles/r04_micro_mainloop_reuse.txt); the block kernel at d = 4 ... 2048 1.40 ms against 1.46 (profiles/r04_tcn_forms_reuse.log).
-// On entry ring[0..3] = windows 0..3 of (c, kk = 0) and A0 = the fragments of (c, kk = 0); on exit the same for class cn (LAST: the
-// next tile's image may not have landed yet - no window of it is read here; A0 is the next tile's first phase: the same weights).
+// base16x16, profiles/r04_micro_mainloop_reuse.txt); round 4's block kernel at d = 4 ... 2048 1.40 ms against 1.46 (profiles/r04_tcn_forms_reuse.log).
+// On entry ring[0..3] = windows 0..3 of (c, kk = 0) and A0 = the fragments of (c, kk = 0); on exit the same for class cn.  LAST = the tile's
+// last class: nothing is fetched behind it - no window, and not the first weight fragments of class cn (32 KB per workgroup, 6.5 % of the
+// tile's weight stream).
 // ------------------------------------------------------------------------------------------------
-// WRAP = false (one tile per workgroup): behind the last class there is no next tile - its first weight fragments (32 KB per workgroup, 6.5 % of
-// the tile's weight stream) are not requested.
-template <int P, int NU, bool LAST, int NUMAX, bool WRAP>
+template <int P, int NU, bool LAST, int NUMAX>
 __device__ __forceinline__ void tcn_reuse_class(f32x4 (&acc)[2][16], bf16x8 (&A0)[NUMAX][2], bf16x8 (&A1)[NUMAX][2], bf16x8 (&ring)[4],
                                                 const unsigned char *sm, const MstStream16 &wst, unsigned aoff, int c, int cn, int l16, int g) {
     constexpr int NW = 15 + NU, NCLS = 16 / P;
@@ -563,7 +562,7 @@ __device__ __forceinline__ void tcn_reuse_class(f32x4 (&acc)[2][16], bf16x8 (&A0
 #pragma unroll
         for (int u = 0; u < NUMAX; ++u) {
             if (kk < 3 && u >= NU) continue;
-            if (LAST && !WRAP && kk == 3) continue;
+            if (LAST && kk == 3) continue;
             int j = (kk < 3 ? c : cn) + NCLS * u;
             j = j < 15 ? j : 14;                                   // the last class has one tap less: that slot holds a fragment nobody uses
             const unsigned so = (unsigned)(j * 4 + (kk < 3 ? kk + 1 : 0)) * 8192u;
@@ -589,433 +588,6 @@ __device__ __forceinline__ void tcn_reuse_class(f32x4 (&acc)[2][16], bf16x8 (&A0
                 ring[n & 3] = *(const bf16x8 *)(rowbn + ((g ^ rswn) << 4) + i2 * 4096);
             __builtin_amdgcn_sched_barrier(0);
         }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// blocks 1..n-1, bf16: the PERSISTENT DOUBLE-TILE form of tcn_block_bf16_kernel ("duo" kernel, round 3) - same tiles, same LDS image, same
-// main loop and epilogue arithmetic, bit-identical results; what changes is who does what:
-//   * ONE workgroup of EIGHT waves per CU, persistent, walking its share of the tiles of one XCD's contiguous tile range;
-//   * waves 0-3 (one per SIMD) are the MATRIX waves: main loop, epilogue arithmetic, transposed tile -> LDS.  They issue no staging
-//     load, no DMA and no global store;
-//   * waves 4-7 (one per SIMD) are the LOADER waves: while the matrix waves work on tile i (buffer i & 1) they store tile i - 1 out of
-//     the other buffer (whole 256-byte rows) and then refill that buffer with tile i + 1 by LDS-DMA (global_load_lds_dwordx4: no VGPR
-//     round trip, no ds_write; the XOR swizzle of the LDS image sits on the SOURCE side: lane l of a 4-row piece fetches slot
-//     (l & 15) ^ (row & 15)).  An LDS-DMA piece occupies its wave for ~100-150 clocks at issue - on a loader wave that is free;
-//   * TWO tile buffers (2 x 78 KB at P = 4) and two workgroup barriers per tile: (1) the matrix waves are done reading tile i AND
-//     tile i + 1 has landed, (2) the transposed output tile is complete.
-// Measured motivation (MI355X, 32 x 131072, d = 4 ... 2048; profiles/r03_tcn_block_forms_summary.md): the main loop alone runs at
-// 1.27 ms per launch at one wave per SIMD as at two; the one-tile-per-workgroup kernel 1.50-1.53 ms; a first persistent double-tile
-// form whose four waves did everything themselves 1.60 ms (0.2 ms for issuing the copy, 0.2 ms for the epilogue).
-// ------------------------------------------------------------------------------------------------
-template <int P, bool FUSE_OUT, int NQ, bool REUSE = false, bool FUSE0 = false>
-__global__ __launch_bounds__(512, 1) void tcn_block_bf16_duo_kernel(TcnBlockArgs a) {
-    static_assert(!REUSE || ((P == 4 || P == 2) && NQ == 8), "the class-major main loop is written for 256-time tiles of two / four phases");
-    static_assert(!FUSE0 || (P == 2 && NQ == 8 && !FUSE_OUT), "block 0 is fused into the d = 2 block's two-phase tiles (consecutive samples)");
-    constexpr int T = 32 * NQ, R = T + 14 * P, R4 = (R + 3) / 4 * 4, MT = T / P, NC = 2 * NQ;
-    constexpr int NK = R4 / 4;                   // 1 KB DMA pieces (4 rows x 256 B) per tile
-    constexpr int NI = (NK + 3) / 4;             // pieces per loader wave
-    constexpr int BUF = R4 * 256;
-    static_assert(2 * BUF + 2048 <= 160 * 1024, "two tiles + parameters fit the CU's LDS");
-    __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * BUF];
-    __shared__ __attribute__((aligned(16))) float par[4 * 128];     // shift | FiLM r | FiLM b | res
-    constexpr int XWP = 304;                                         // FUSE0: waveform samples per channel a tile needs (R + 14 = 298), padded
-    __shared__ float xs0[FUSE0 ? 4 * 2 * XWP : 1];                   // FUSE0: one private waveform window per loader wave
-    __shared__ __attribute__((aligned(16))) float par0[FUSE0 ? 4 * 128 : 4];          // FUSE0: block 0's shift | FiLM r | FiLM b | res for the loader waves
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool loader = wv >= 4;
-    const int w = wv & 3;                        // matrix wave: its channel quarter; loader wave: its share of pieces / rows
-    const int l16 = lane & 15, g = lane >> 4;
-
-    // ---- this workgroup's tiles: workgroup i runs on XCD i % 8 and walks tiles (i % 8) * xcd_tiles + i / 8 + n * gridDim.x / 8
-    // (32-bit tile numbers - the launcher checks the count: a 64-bit division is ~100 instructions, taken from the matrix wave's issue slots)
-    const unsigned ntiles = (unsigned)a.B * (unsigned)a.tiles_phase * (unsigned)a.tiles_step;
-    unsigned tile, tstep, tend;
-    if (a.xcd_tiles > 0) {
-        tile = (blockIdx.x & 7) * (unsigned)a.xcd_tiles + (blockIdx.x >> 3);
-        tstep = gridDim.x >> 3;
-        tend = ((blockIdx.x & 7) + 1) * (unsigned)a.xcd_tiles;
-        if (tend > ntiles) tend = ntiles;
-    } else {
-        tile = blockIdx.x;
-        tstep = gridDim.x;
-        tend = ntiles;
-    }
-    if (tile >= tend) return;       // uniform
-
-    auto tile_geometry = [&](unsigned tl, int &b, int &m0, int &phi0) {
-        const unsigned r = tl / (unsigned)a.tiles_step, mg = tl - r * (unsigned)a.tiles_step;
-        const unsigned bb = r / (unsigned)a.tiles_phase;
-        phi0 = (int)(r - bb * (unsigned)a.tiles_phase) * P;
-        b = (int)bb;
-        m0 = (int)mg * MT;
-    };
-    // loader waves: all pieces of tile (b, m0, phi0) that belong to this wave (k = w mod 4), into buffer buf.  A tile that lies inside the
-    // segment (all but the first / last of a phase group) needs no bounds test: the pieces of a wave are 16 rows = 16 / P steps apart,
-    // one 64-bit add per piece (the loader shares its SIMD's issue slots with a matrix wave: every instruction here is taken from it)
-    auto dma_tile = [&](int b, int m0, int phi0, int buf) {
-        static_assert(16 % P == 0, "pieces advance by a whole number of steps");
-        const int row0 = 4 * w + (lane >> 4);
-        const long t0 = (long)(m0 + row0 / P - 7) * a.d + phi0 + (row0 % P);
-        const long dt = (long)(16 / P) * a.d;
-        const int slot = (lane & 15) ^ (row0 & 15);          // row & 15 is the same for all pieces of a lane
-        const long t_first = (long)(m0 - 7) * a.d + phi0, t_last = (long)(m0 + (R4 - 1) / P - 7) * a.d + phi0 + (P - 1);
-        unsigned char *dst = smem + buf * BUF + w * 1024;
-        if (t_first >= 0 && t_last < a.L) {                   // uniform
-            const unsigned char *src = (const unsigned char *)a.x + ((size_t)b * a.Lp + t0) * 256 + slot * 16;
-#pragma unroll 1
-            for (int k = w; k < NK; k += 4) {
-                mst_dma16(src, dst);
-                src += dt * 256;
-                dst += 4096;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-                const int row = row0 + 16 * i;
-                const long t = t0 + i * dt;
-                const bool ok = row < R && t >= 0 && t < a.L;
-                const unsigned char *src = (ok ? (const unsigned char *)a.x + ((size_t)b * a.Lp + t) * 256 : (const unsigned char *)a.zeros) + slot * 16;
-                if (w + 4 * i < NK) mst_dma16(src, dst + i * 4096);
-            }
-        }
-    };
-    // FUSE0, loader waves: the rows of tile (b, m0) are block 0's outputs at the consecutive times t_first + r (d = P = 2, one phase group) -
-    // computed here exactly like tcn_block0_mfma_kernel computes them (same fragments, same MFMA order, same epilogue: the same bits) and
-    // written where the DMA would have put them; rows outside the segment are zero rows (this block's padding).  Loader wave w owns the
-    // 32-row column tiles q = w, w + 4, w + 8 of the image - ALL 128 channels of them, and (see the store phase) the same rows of the
-    // output tile: a wave only overwrites rows it has stored out itself, no barrier between the loader waves.  Its waveform window is its own.
-    auto compute_tile0 = [&](int b, int m0, int phi0, int buf) {
-        if constexpr (FUSE0) {
-            const int ln = lane & 31, h = lane >> 5;
-            float *xw0 = xs0 + w * 2 * XWP, *xw1 = xw0 + XWP;
-            const long t_first = (long)(m0 - 7) * a.d + phi0;           // time of row 0
-            __builtin_amdgcn_wave_barrier();          // every lane is past its reads of the rows / the window this call overwrites
-            for (int i = lane; i < 2 * XWP; i += 64) {
-                const int ci = i >= XWP ? 1 : 0, k = i - ci * XWP;
-                const long t = t_first - 7 + k;
-                (ci ? xw1 : xw0)[k] = (t >= 0 && t < a.L) ? a.x0[((size_t)b * 2 + ci) * a.L + t] : 0.0f;
-            }
-            unsigned char *img = smem + buf * BUF;
-            // block 0's parameters with the FiLM row of item b: ONE copy that every loader wave writes in full - they fill the same tile between the
-            // same two workgroup barriers, so concurrent writers write the same values, and a wave reads behind its own fence
-            float *pw = par0;
-            {
-                const float *frow0 = a.film0 + (a.film_rows > 1 ? (size_t)b * 256 : 0);
-                for (int i = lane; i < 128; i += 64) {
-                    pw[i] = a.shift0[i];
-                    pw[128 + i] = frow0[i];
-                    pw[256 + i] = frow0[128 + i];
-                    pw[384 + i] = a.res0[i];
-                }
-            }
-            mst_wave_lds_fence();                                       // the window and the parameters are in LDS
-            const bf16x8 *const w0p = (const bf16x8 *)a.w0pk + lane;
-            // rows 0 .. 255 (the rows the store phase reads): 32-row groups w and w + 4, all four channel quarters; the halo group 8 (rows 256 ..
-            // 283, never stored) is shared: every wave computes ITS quarter of it - nine (group, quarter) units per wave
-            static_assert((R + 31) / 32 == 9, "eight stored row groups + one halo group");
-#pragma unroll 1
-            for (int q = w; q < 12; q += 4) {
-                const bool halo = q >= 8;                                  // third trip: group 8, one quarter
-                if (halo) q = 8;
-                bf16x8 bh[2], bl[2];
-#pragma unroll
-                for (int sI = 0; sI < 2; ++sI) tcn_block0_bfrag(xw0, xw1, 32 * q + ln, sI, h, bh[sI], bl[sI]);
-                const int o = 32 * q + ln;
-                const long t = t_first + o;
-                const bool inside = t >= 0 && t < a.L;
-#pragma unroll 1
-                for (int cw = halo ? w : 0; cw < (halo ? w + 1 : 4); ++cw) {      // channel quarters (what the four waves of the block-0 kernel do)
-                    f32x16 acc;
-#pragma unroll
-                    for (int gq = 0; gq < 4; ++gq) {
-                        const f32x4 sh = *(const f32x4 *)(pw + 32 * cw + 8 * gq + 4 * h);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) acc[4 * gq + i] = sh[i];
-                    }
-#pragma unroll
-                    for (int sI = 0; sI < 2; ++sI) {
-                        const bf16x8 af = w0p[(sI ? 256 : 0) + 64 * cw];
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bh[sI], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bl[sI], acc, 0, 0, 0);
-                    }
-                    const float xres = ((cw >> 1) ? xw1 : xw0)[o + 7];      // grouped residual: channels 0..63 read input 0, 64..127 input 1
-#pragma unroll
-                    for (int gq = 0; gq < 4; ++gq) {
-                        const int co0 = 32 * cw + 8 * gq + 4 * h;
-                        const f32x4 fr = *(const f32x4 *)(pw + 128 + co0);
-                        const f32x4 fb = *(const f32x4 *)(pw + 256 + co0);
-                        const f32x4 rs = *(const f32x4 *)(pw + 384 + co0);
-                        bf16x4 out;
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) out[i] = inside ? tcn_block0_out(acc[4 * gq + i], fr[i], fb[i], rs[i], xres) : (__bf16)0.0f;
-                        if (o < R) *(bf16x4 *)(img + o * 256 + (((co0 >> 3) ^ (o & 15)) << 4) + 8 * h) = out;
-                    }
-                }
-            }
-        }
-    };
-    auto fill_tile = [&](int b, int m0, int phi0, int buf) {
-        if constexpr (FUSE0) compute_tile0(b, m0, phi0, buf);
-        else dma_tile(b, m0, phi0, buf);
-    };
-    auto stage_film = [&](int b) {          // matrix waves only (tid < 256)
-        if (tid < 128) {
-            const float *frow0 = a.film + (a.film_rows > 1 ? (size_t)b * 256 : 0);
-            par[128 + tid] = frow0[tid];
-            par[256 + tid] = frow0[128 + tid];
-        }
-    };
-
-    int tb, tm0, tphi0;
-    tile_geometry(tile, tb, tm0, tphi0);
-    if (loader) {
-        fill_tile(tb, tm0, tphi0, 0);
-    } else {
-        if (tid < 128) {
-            par[tid] = a.shift[tid];
-            par[384 + tid] = a.res[tid];
-        }
-        stage_film(tb);
-    }
-    mst_dma_wait_barrier<0>();
-
-    if (loader) {
-        // =================================================================== loader waves
-        // iteration i: [next tile -> the other buffer] (barrier 1 of tile i) (barrier 2 of tile i) [tile i's output rows -> global memory]
-        int cur = 0;
-        const int lt = tid - 256;                      // 0..255: thread (prow, slot) of the row passes, like the one-tile kernel's
-        for (;;) {
-            const int b = tb, m0 = tm0, phi0 = tphi0;
-            const unsigned tnext = tile + tstep;
-            const bool has_next = tnext < tend;
-            if (has_next) {
-                tile_geometry(tnext, tb, tm0, tphi0);
-                fill_tile(tb, tm0, tphi0, cur ^ 1);     // the buffer whose rows this wave stored out itself one iteration ago
-            }
-            mst_dma_wait_barrier<0>();                  // (1) the next tile has landed (and this wave's stores have left)
-            if constexpr (FUSE_OUT) {
-                mst_dma_wait_barrier<63>();             // (2a) the output head's partial sums are complete (matrix waves finish the tile)
-                mst_dma_wait_barrier<63>();             // (2b) ... and have been read: the buffer may be refilled
-            } else {
-                mst_dma_wait_barrier<63>();             // (2) the transposed output tile is complete
-                const unsigned char *sm = smem + cur * BUF;
-                __bf16 *yb = (__bf16 *)a.y + (size_t)b * a.Lp * 128;
-                if constexpr (FUSE0) {
-                    // loader wave w stores the rows it will overwrite with the next tile: the 32-row groups q = w, w + 4 (d = P = 2: row o is time 2 m0 + o)
-                    const int slot = lane & 15, rsub = lane >> 4;
-#pragma unroll
-                    for (int qq = 0; qq < 2; ++qq)
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) {
-                            const int o = 32 * (w + 4 * qq) + rsub + 4 * i;
-                            const long t = (long)(m0 + o / P) * a.d + phi0 + (o % P);
-                            if (t < a.L) *(bf16x8 *)(yb + t * 128 + slot * 8) = *(const bf16x8 *)(sm + o * 256 + ((slot ^ (o & 15)) << 4));
-                        }
-                } else {
-                const int slot = lt & 15, prow = lt >> 4;
-                const long dt = (long)(16 / P) * a.d;
-                long t = (long)(m0 + prow / P) * a.d + phi0 + (prow % P);
-                __bf16 *dstp = yb + t * 128 + slot * 8;
-                const unsigned char *srcp = sm + prow * 256 + ((slot ^ (prow & 15)) << 4);
-                if ((long)(m0 + (T - 1) / P) * a.d + phi0 + (P - 1) < a.L) {        // uniform: every row of the tile is inside the segment
-#pragma unroll
-                    for (int i = 0; i < T / 16; ++i) {
-                        *(bf16x8 *)dstp = *(const bf16x8 *)(srcp + i * 4096);
-                        dstp += dt * 128;
-                    }
-                } else {
-#pragma unroll
-                    for (int i = 0; i < T / 16; ++i) {
-                        if (t < a.L) *(bf16x8 *)dstp = *(const bf16x8 *)(srcp + i * 4096);
-                        t += dt;
-                        dstp += dt * 128;
-                    }
-                }
-                }
-            }
-            if (!has_next) break;
-            tile = tnext;
-            cur ^= 1;
-        }
-        return;
-    }
-
-    // ======================================================================= matrix waves
-    __builtin_amdgcn_s_setprio(2);          // the loader wave of the SIMD takes the issue slots this wave leaves, never the other way round
-    // A fragments: wpk[ks = j*4 + kk][row tile m][wave][lane] = 8 bf16; a ring of four k-steps that runs on across tiles (every tile
-    // multiplies by the same weights: behind the last tap the fragments of tap 0 are requested again)
-    const MstStream16 wst = mst_stream16(a.wpk, 60u * 2u * 4096u);
-    const unsigned aoff = (unsigned)(w * 64 + lane) * 16u;
-    constexpr int RB = 8;
-    static_assert(NC % RB == 0, "the ring divides the column tiles");
-    bf16x8 af[2][4], bf[RB];
-    constexpr int NCLS = 16 / P, NUMAX = (15 + NCLS - 1) / NCLS;      // REUSE: tap classes, taps per class (the last class: 15 / NCLS)
-    bf16x8 A0[NUMAX][2], A1[NUMAX][2], ring[4];                      // REUSE: the class-major loop's operands (tcn_reuse_class)
-    if constexpr (REUSE) {
-#pragma unroll
-        for (int u = 0; u < NUMAX; ++u) {
-#pragma unroll
-            for (int m = 0; m < 2; ++m) A0[u][m] = __builtin_bit_cast(bf16x8, mst_stream_load16(wst, aoff + m * 4096, (unsigned)(4 * NCLS * u) * 8192u));
-        }
-    } else {
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-#pragma unroll
-            for (int m = 0; m < 2; ++m) af[m][kk] = __builtin_bit_cast(bf16x8, mst_stream_load16(wst, aoff + m * 4096, (unsigned)kk * 8192u));
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-
-    int cur = 0, bprev = tb;
-    // (round 5, phase clocks of this wave - tools/probe_tcn_phases.py: the per-tile bookkeeping, i.e. the two 32-bit divisions of
-    //  tile_geometry, cost 1250 of the tile's 42 600 clocks.  A matrix wave needs the next tile's coordinates only for the fused output
-    //  head; otherwise only its batch item, and that only when every item has its own FiLM row: one division, or none)
-    const unsigned tiles_item = (unsigned)a.tiles_phase * (unsigned)a.tiles_step;
-    for (;;) {
-        const int b = tb, m0 = tm0, phi0 = tphi0;
-        const unsigned tnext = tile + tstep;
-        const bool has_next = tnext < tend;
-        if (has_next) {
-            if constexpr (FUSE_OUT) tile_geometry(tnext, tb, tm0, tphi0);
-            else if (a.film_rows > 1) tb = (int)(tnext / tiles_item);
-        }
-        unsigned char *const sm = smem + cur * BUF;
-        if (b != bprev) {              // a new batch item: its FiLM row (every matrix wave is past the previous tile's epilogue: barrier 2)
-            stage_film(b);
-            bprev = b;
-        }
-
-        f32x4 acc[2][NC];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {          // the accumulators start from the BN shift of their channel
-            const f32x4 sh = *(const f32x4 *)(par + 32 * w + 16 * m + 4 * g);
-#pragma unroll
-            for (int q = 0; q < NC; ++q) acc[m][q] = sh;
-        }
-        if constexpr (REUSE) {
-            {
-                const unsigned char *rp0 = sm + l16 * 256 + ((g ^ l16) << 4);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) ring[i] = *(const bf16x8 *)(rp0 + i * 4096);
-            }
-#pragma unroll 1
-            for (int c = 0; c < NCLS - 1; ++c) tcn_reuse_class<P, NUMAX, false, NUMAX>(acc, A0, A1, ring, sm, wst, aoff, c, c + 1, l16, g);
-            tcn_reuse_class<P, 15 / NCLS, true, NUMAX>(acc, A0, A1, ring, sm, wst, aoff, NCLS - 1, 0, l16, g);
-        } else {
-        {
-            const unsigned char *rp0 = sm + l16 * 256 + ((g ^ l16) << 4);
-#pragma unroll
-            for (int q = 0; q < RB; ++q) bf[q] = *(const bf16x8 *)(rp0 + q * 4096);
-        }
-#pragma unroll 1
-        for (int j = 0; j < 15; ++j) {
-            const int jn = j < 14 ? j + 1 : 0;
-            const int rb0 = j * P + l16, rb1 = (j < 14 ? j + 1 : 14) * P + l16;
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const int rbn = (kk == 3) ? rb1 : rb0;
-                const int kn = (kk + 1) & 3;
-                const unsigned char *cp = sm + rb0 * 256 + (((4 * kk + g) ^ (rb0 & 15)) << 4);
-                const unsigned char *np = sm + rbn * 256 + (((4 * kn + g) ^ (rbn & 15)) << 4);
-#pragma unroll
-                for (int q = 0; q < NC; ++q) {
-                    acc[0][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0][kk], bf[q % RB], acc[0][q], 0, 0, 0);
-                    acc[1][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1][kk], bf[q % RB], acc[1][q], 0, 0, 0);
-                    bf[q % RB] = (q + RB < NC) ? *(const bf16x8 *)(cp + (q + RB) * 4096) : *(const bf16x8 *)(np + (q + RB - NC) * 4096);
-                    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                }
-#pragma unroll
-                for (int m = 0; m < 2; ++m) af[m][kk] = __builtin_bit_cast(bf16x8, mst_stream_load16(wst, aoff + m * 4096, (unsigned)(jn * 4 + kk) * 8192u));
-                __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
-            }
-        }
-        }
-
-        // ---- epilogue arithmetic (the one of tcn_block_bf16_kernel): residual rows -> registers, barrier, transposed tile -> LDS, barrier
-        // (the residual rows of row tile 1 are read behind the barrier: they sit in this wave's own channel columns, which no other wave
-        //  writes and which its own row-tile-0 results do not touch - 32 registers instead of 64 next to the accumulators)
-        // (lane coordinates made opaque once per tile: otherwise hipcc keeps ~36 tile-invariant LDS addresses of this epilogue live across
-        //  the main loop - and, at the 256-register limit of an eight-wave workgroup, spills them)
-        int l16e = l16, ge = g;
-        asm volatile("" : "+v"(l16e), "+v"(ge));
-        bf16x4 xin[NC];
-        auto read_xin = [&](int m) {
-            const int co0 = 32 * w + 16 * m + 4 * ge;
-#pragma unroll
-            for (int q = 0; q < NC; ++q) {
-                const int row = 16 * q + l16e + 7 * P;
-                xin[q] = *(const bf16x4 *)(sm + row * 256 + (((co0 >> 3) ^ (row & 15)) << 4) + 2 * (co0 & 7));
-            }
-        };
-        read_xin(0);
-        mst_dma_wait_barrier<63>();            // (1) every matrix wave is done reading this tile (the weight fragments in flight stay in flight)
-        float hs0[NC], hs1[NC];
-#pragma unroll
-        for (int q = 0; q < NC; ++q) hs0[q] = hs1[q] = 0.0f;
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            if (m) {
-                read_xin(1);
-                __builtin_amdgcn_wave_barrier();      // all lanes of the wave have read before any of them writes these columns (lockstep on the GPU)
-            }
-            const int co0 = 32 * w + 16 * m + 4 * ge;
-            const f32x4 fr = *(const f32x4 *)(par + 128 + co0);
-            const f32x4 fb = *(const f32x4 *)(par + 256 + co0);
-            const f32x4 rs = *(const f32x4 *)(par + 384 + co0);
-            f32x4 ow0 = {0.0f, 0.0f, 0.0f, 0.0f}, ow1 = {0.0f, 0.0f, 0.0f, 0.0f};
-            if constexpr (FUSE_OUT) {
-                ow0 = *(const f32x4 *)(a.out_w + co0);
-                if (a.nout > 1) ow1 = *(const f32x4 *)(a.out_w + 128 + co0);
-            }
-#pragma unroll
-            for (int q = 0; q < NC; ++q) {
-                const int o = 16 * q + l16e;
-                const float v4[4] = {acc[m][q][0], acc[m][q][1], acc[m][q][2], acc[m][q][3]};
-                const bf16x4 out = tcn_epilogue4(v4, fr, fb, rs, xin[q]);
-                if constexpr (FUSE_OUT) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        hs0[q] = fmaf(ow0[i], (float)out[i], hs0[q]);
-                        hs1[q] = fmaf(ow1[i], (float)out[i], hs1[q]);
-                    }
-                }
-                if constexpr (!FUSE_OUT) *(bf16x4 *)(sm + o * 256 + (((co0 >> 3) ^ (o & 15)) << 4) + 2 * (co0 & 7)) = out;
-            }
-        }
-        if constexpr (FUSE_OUT) {
-            float *part = (float *)sm;                 // [4 waves][2 outputs][T columns]
-#pragma unroll
-            for (int q = 0; q < NC; ++q) {
-                hs0[q] += __shfl_xor(hs0[q], 16);
-                hs1[q] += __shfl_xor(hs1[q], 16);
-                hs0[q] += __shfl_xor(hs0[q], 32);
-                hs1[q] += __shfl_xor(hs1[q], 32);
-                if (g == 0) {
-                    part[(w * 2 + 0) * T + 16 * q + l16] = hs0[q];
-                    part[(w * 2 + 1) * T + 16 * q + l16] = hs1[q];
-                }
-            }
-            mst_dma_wait_barrier<63>();          // (2a)
-#pragma unroll
-            for (int i = 0; i < 2 * T / 256; ++i) {
-                const int idx = tid + 256 * i, c = idx / T, o = idx % T;
-                const long t = (long)(m0 + o / P) * a.d + phi0 + (o % P);
-                if (c < a.nout && t < a.L) {
-                    const float v = part[(0 * 2 + c) * T + o] + part[(1 * 2 + c) * T + o] + part[(2 * 2 + c) * T + o] +
-                                    part[(3 * 2 + c) * T + o] + a.out_b[c];
-                    a.y_out[((size_t)b * a.nout + c) * a.L + t] = fminf(1.0f, fmaxf(-1.0f, v));
-                }
-            }
-            mst_dma_wait_barrier<63>();          // (2b) the partial sums have been read: the loader waves may refill this buffer
-        } else {
-            mst_dma_wait_barrier<63>();          // (2) the transposed output tile is complete: the loader waves store it
-        }
-        if (!has_next) break;
-        tile = tnext;
-        cur ^= 1;
     }
 }
 
@@ -2028,8 +1600,8 @@ __global__ void tcn_unpack_kernel(const void *x, float *y, int B, int L, int Lp)
 }
 
 // ------------------------------------------------------------------------------------------------
-// Calibration of the box (bench.py "roofline.calib_ms"): the BARE MAIN LOOP of tcn_block_bf16_duo_kernel - v_mfma_f32_16x16x32_bf16 with the
-// product loop's operand traffic (class-major since round 4's last third: 128 weight fragments from L2 and 304 B fragments from LDS per
+// Calibration of the box (bench.py "roofline.calib_ms"): the BARE MAIN LOOP of the bf16 block kernel's four-phase class-major tiles
+// (tcn_block_bf16_kernel<4, ., 8, 2>) - v_mfma_f32_16x16x32_bf16 with the product loop's operand traffic (class-major since round 4's last third: 128 weight fragments from L2 and 304 B fragments from LDS per
 // 1920 MFMAs; before: 120 and 960 - the tap-major loop; same box 1.230 -> 1.145 ms, profiles/r04_micro_mainloop_reuse.txt, so calib_ms
 // values of earlier records are 7 % higher for the same box), no staging, no epilogue, no store - on synthetic operands with realistic statistics (activations ~ N(0, 0.5^2), weights ~ N(0, 0.05^2): the chip's power limit
 // depends on the operand bits).  512 workgroups x `rep` tiles of 256 times: rep = 32 is exactly the arithmetic of one dense TCN block
@@ -2065,7 +1637,7 @@ __global__ __launch_bounds__(256, 2) void tcn_calib_mainloop_kernel(const void *
     for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int q = 0; q < 16; ++q) acc[m][q] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    // the class-major loop of the duo kernel's four-phase tiles (tcn_reuse_class), tile after tile on the same LDS image
+    // the class-major loop of the four-phase 256-time tiles (tcn_reuse_class), tile after tile on the same LDS image
     const MstStream16 wst = mst_stream16(wpk, 60u * 2u * 4096u);
     const unsigned aoff = (unsigned)(w * 64 + lane) * 16u;
     bf16x8 A0[4][2], A1[4][2], ring[4];

@@ -85,16 +85,17 @@ def test_tcn_bf16_whole_sequence_tiles_emulated(emu_default):
         assert float((a - col[3]).abs().max()) <= 4e-2 * float(col[3].abs().max())
 
 
-def test_tcn_bf16_duo_kernel_emulated(emu_default):
-    """The persistent LDS-DMA-fed form of the bf16 block kernel (mst_tcn_set_tuning bits 1-2 = 2, "duo") in its tap-major order (bit 4 off): the
-    one-tile-per-workgroup kernel's arithmetic in the same order - bit-identical - and the oracle at the bf16 tolerance.  The emulated grid
-    has 8 workgroups: several tiles per workgroup, XCD-ordered tile ranges, every phase count P, per-item FiLM rows, the fused output head.
-    (Form 1, the "stream" kernel, and bit 3, the split-bf16 duo kernel, left the library in round 5: the setter rejects them.)"""
+def test_tcn_bf16_tap_major_form_emulated(emu_default):
+    """Form 0 of the bf16 block kernel (mst_tcn_set_tuning bits 1-2 = 0: tcn_block_bf16_kernel's tap-major loop for every block) against the
+    oracle at the bf16 tolerance: the emulated grid has 8 workgroups - XCD-ordered tiles, every phase count P, per-item FiLM rows, the fused
+    output head.  Blocks of odd dilation (P = 1) run that same form under the default flags: bit for bit.  The setter rejects what selected
+    kernels that left the library: form 1, form 3, bit 3, and form 2 without bit 4."""
     cond = synth.synth_audio((1, 64), seed=2)
     cases = [(4, 2, (2, 2, 777), cond),                                   # P = 2, 4, 8; 2 x 8 tiles over 8 workgroups
              (4, 3, (1, 2, 300), cond),                                   # odd dilations: P = 1
              (6, 2, (1, 2, 200), cond),                                   # short segment: P = 8 / 16 tiles, zero rows, skipped column tiles
              (3, 2, (3, 2, 1500), synth.synth_audio((3, 64), seed=11))]   # 3 x 6 tiles: uneven walks, one FiLM row per item
+    from music_mixing_style_transfer_amd import _lib
     for nb, growth, shape, cnd in cases:
         m, sd = _tcn(nb, growth=growth)
         m.precision = "bf16"
@@ -102,22 +103,21 @@ def test_tcn_bf16_duo_kernel_emulated(emu_default):
         col = []
         y_ref = R.tcn_forward(sd, x, cnd, nblocks=nb, dilation_growth=growth, collect=col)
         m._ensure(emu_default)
-        emu_default.check(emu_default.mst_tcn_set_tuning(m._handle, 1), "tuning")           # form 0: one tile per workgroup
+        emu_default.check(emu_default.mst_tcn_set_tuning(m._handle, 1), "tuning")           # form 0: tap-major everywhere
         y0 = m(x, cnd)
         a0 = m.forward_blocks(x, cnd, nb)
         assert float((y0 - y_ref).abs().max()) <= 4e-2
         assert float((a0 - col[nb - 1]).abs().max()) <= 4e-2 * float(col[nb - 1].abs().max())
-        # form 2 ("duo": 4 matrix + 4 loader waves per CU, two tile buffers, the next tile by LDS-DMA during the main loop), tap-major:
-        # the same bits as form 0
-        emu_default.check(emu_default.mst_tcn_set_tuning(m._handle, 5), "tuning")
-        assert torch.equal(m(x, cnd), y0) and torch.equal(m.forward_blocks(x, cnd, nb), a0)
-    for gone in (3, 6, 13):          # the stream kernel (form 1), form 3, the split-bf16 duo kernel (bit 3)
+        if growth == 3:          # odd dilations: every dense block has P = 1 - the default flags run form 0's kernel on them
+            emu_default.check(emu_default.mst_tcn_set_tuning(m._handle, _lib.TCN_TUNING_DEFAULT), "tuning")
+            assert torch.equal(m(x, cnd), y0) and torch.equal(m.forward_blocks(x, cnd, nb), a0)
+    for gone in (3, 6, 13, 5, 37):          # form 1, form 3, bit 3; form 2 without bit 4 (the tap-major loop of round 3's persistent kernel)
         with pytest.raises(ValueError):
             emu_default.check(emu_default.mst_tcn_set_tuning(m._handle, gone), "tuning")
 
 
-def test_tcn_bf16_duo_reuse_main_loop_emulated(emu_default):
-    """The class-major main loop of the duo kernel's four-phase tiles (mst_tcn_set_tuning bit 4): every B fragment is read from LDS once per
+def test_tcn_bf16_class_major_main_loop_emulated(emu_default):
+    """The class-major main loop of the four-phase 256-time tiles (mst_tcn_set_tuning form 2): every B fragment is read from LDS once per
     class of taps (j mod 4) and feeds up to eight MFMAs; same products as the tap-major loop, summed in another order - against the oracle at
     the bf16 tolerance, against the tap-major form to accumulation rounding.  d = 4 ... 32 at lengths that give four-phase tiles: several
     tiles per workgroup, ragged last tiles (zero rows), tiles of more than one phase group, one FiLM row per item."""
@@ -132,7 +132,7 @@ def test_tcn_bf16_duo_reuse_main_loop_emulated(emu_default):
         col = []
         y_ref = R.tcn_forward(sd, x, cnd, nblocks=nb, dilation_growth=growth, collect=col)
         m._ensure(emu_default)
-        emu_default.check(emu_default.mst_tcn_set_tuning(m._handle, 5), "tuning")            # tap-major
+        emu_default.check(emu_default.mst_tcn_set_tuning(m._handle, 1), "tuning")            # tap-major (form 0)
         y0, a0 = m(x, cnd), m.forward_blocks(x, cnd, nb)
         emu_default.check(emu_default.mst_tcn_set_tuning(m._handle, 21), "tuning")           # class-major
         y1, a1 = m(x, cnd), m.forward_blocks(x, cnd, nb)
@@ -144,9 +144,9 @@ def test_tcn_bf16_duo_reuse_main_loop_emulated(emu_default):
 
 
 def test_tcn_bf16_one_tile_class_major_256_time_tiles_emulated(emu_default):
-    """mst_tcn_set_tuning bit 7 (round 6, default): the four-phase class-major blocks on the ONE-TILE kernel's 256-time tiles (two workgroups
-    per CU) instead of the duo kernel - the duo kernel's products in the duo kernel's order: bit-identical, several tiles per phase sequence,
-    ragged last tiles, per-item FiLM rows; and against the oracle at the bf16 tolerance."""
+    """mst_tcn_set_tuning bit 7 (round 6, default) on a four-phase LAST block (fused output head): the class-major loop of the one-tile kernel's
+    256-time tiles instead of the tap-major one - the same products in another fp32 order; several tiles per phase sequence, ragged last
+    tiles, per-item FiLM rows; against the oracle at the bf16 tolerance.  Blocks without the head run the same kernel either way."""
     cases = [(4, (2, 2, 1500), synth.synth_audio((2, 64), seed=11)),        # d = 4, 8: 6 / 3 tiles per sequence, the last ragged
              (5, (1, 2, 2100), synth.synth_audio((1, 64), seed=2))]         # d = 4, 8, 16 (d = 16: 132 steps = 3 tiles, the last ragged)
     for nb, shape, cnd in cases:
@@ -155,14 +155,13 @@ def test_tcn_bf16_one_tile_class_major_256_time_tiles_emulated(emu_default):
         x = synth.synth_audio(shape, seed=1)
         y_ref = R.tcn_forward(sd, x, cnd, nblocks=nb)
         m._ensure(emu_default)
-        emu_default.check(emu_default.mst_tcn_set_tuning(m._handle, 21), "tuning")           # duo, class-major
-        y0, a0 = m(x, cnd), m.forward_blocks(x, cnd, nb - 1)
+        emu_default.check(emu_default.mst_tcn_set_tuning(m._handle, 21), "tuning")           # class-major, bit 7 off
+        y0 = m(x, cnd)
         emu_default.check(emu_default.mst_tcn_set_tuning(m._handle, 21 | 128), "tuning")     # + bit 7
         fl = C.c_int(0)
         emu_default.check(emu_default.mst_tcn_get_tuning(m._handle, C.byref(fl), None), "get")
         assert fl.value == 21 | 128
-        y1, a1 = m(x, cnd), m.forward_blocks(x, cnd, nb - 1)
-        assert torch.equal(a0, a1)
+        y1 = m(x, cnd)
         # the waveform: the LAST block (four phases here, fused head) runs the one-tile kernel in both settings - tap-major with bit 7 off, class-major
         # with it: the same products in another fp32 order, re-rounded to bf16 in front of the head
         assert float((y1 - y0).abs().max()) <= 5e-3
@@ -177,7 +176,7 @@ def test_tcn_bf16_whole_sequence_256_time_tiles_emulated(emu_default):
     """Round 6 (with mst_tcn_set_tuning bit 7): a block whose phase sequences are EXACTLY one 256-time tile - 64 steps (four phases), 32 (eight) or 16
     (sixteen: d = 2048 / 4096 / 8192 at L = 131072) - runs the unrolled class-major loop on an LDS image that keeps only the halo steps a row window
     can straddle into (3 / 1 / 0): all-padding windows are neither staged nor read; the sixteen-phase form also with the fused output head (the last
-    block).  At L = 512: d = 8, 16, 32.  The four-phase form sums in the duo kernel's order (bit-identical to bit 7 off); the other two agree with
+    block).  At L = 512: d = 8, 16, 32.  The four-phase form sums in the general class-major tiles' order (bit-identical to bit 7 off); the other two agree with
     round 5's 128-time forms to accumulation rounding (one bf16 ulp on the activation); all within the bf16 tolerance of the oracle."""
     for nb, shape, cnd in [(6, (3, 2, 512), synth.synth_audio((3, 64), seed=11)),        # d = 32 is the last block: fused head
                            (5, (16, 2, 512), synth.synth_audio((1, 64), seed=2))]:      # d = 16 (eight phases) is the last block: its head runs round 5's form
@@ -196,7 +195,7 @@ def test_tcn_bf16_whole_sequence_256_time_tiles_emulated(emu_default):
         for k, n in enumerate(range(3, nb + 1)):
             a1, a0, r = out[181][1 + k], out[53][1 + k], col[n - 1]
             assert float((a1 - r).abs().max()) <= 4e-2 * float(r.abs().max()), n
-            if n <= 4:          # d = 4 (several tiles per sequence), d = 8 (the whole-sequence four-phase tile): the duo kernel's order
+            if n <= 4:          # d = 4 (several tiles per sequence), d = 8 (the whole-sequence four-phase tile): the class-major tiles' order
                 assert torch.equal(a1, a0), n
             else:
                 assert float((a1 - a0).abs().max()) <= 2.0 ** -6 * float(a0.abs().max()), n
@@ -206,10 +205,9 @@ def test_tcn_bf16_whole_sequence_256_time_tiles_emulated(emu_default):
 
 def test_tcn_bf16_block0_fused_into_block1_emulated(emu_default):
     """mst_tcn_set_tuning bit 5 (default): block 0 is not launched - the d = 2 block computes its input rows from the waveform with
-    tcn_block0_mfma_kernel's arithmetic, in the loader waves of the duo kernel (bit 7 off) or in the staging of the one-tile kernel (bit 7, the
-    default since round 6): the same bits as the separate kernel on every activation and on the waveform, in both forms.  Several tiles per
-    workgroup (the duo kernel's buffers are refilled), ragged lengths (zero rows on both sides, a last tile mostly outside the segment), segments
-    shorter than a tile, per-item FiLM rows; probes of block 0 alone stay on the separate kernel."""
+    tcn_block0_mfma_kernel's arithmetic in the staging of the one-tile kernel's two-phase class-major tiles: the same bits as the separate kernel
+    on every activation and on the waveform, with bit 7 on and off.  Several tiles per phase sequence, ragged lengths (zero rows on both sides, a
+    last tile mostly outside the segment), segments shorter than a tile, per-item FiLM rows; probes of block 0 alone stay on the separate kernel."""
     cases = [(4, (2, 2, 777), synth.synth_audio((1, 64), seed=2)),
              (3, (3, 2, 1500), synth.synth_audio((3, 64), seed=11)),
              (3, (2, 2, 41), synth.synth_audio((2, 64), seed=4))]          # (more shapes: tools/emu_sweep_tcn.py --fuse0)
@@ -221,7 +219,7 @@ def test_tcn_bf16_block0_fused_into_block1_emulated(emu_default):
         emu_default.check(emu_default.mst_tcn_set_tuning(m._handle, 21), "tuning")
         y0 = m(x, cnd)
         a0 = [m.forward_blocks(x, cnd, n) for n in (1, 2, nb - 1)]
-        for flags in (21 | 32, 21 | 32 | 128, 21 | 128):          # fused in the duo kernel / in the one-tile kernel; the one-tile kernel unfused
+        for flags in (21 | 32, 21 | 32 | 128, 21 | 128):          # fused with bit 7 off / on; unfused with bit 7
             emu_default.check(emu_default.mst_tcn_set_tuning(m._handle, flags), "tuning")
             y1 = m(x, cnd)
             fl, fused = C.c_int(0), C.c_int(0)
@@ -236,7 +234,7 @@ def test_tcn_bf16_block0_fused_into_block1_emulated(emu_default):
                 assert torch.equal(y1, y0), (shape, flags)
         y_ref = R.tcn_forward(sd, x, cnd, nblocks=nb)
         assert float((y1 - y_ref).abs().max()) <= 4e-2
-    # without the class-major duo form there is nothing to fuse into: the flag is ignored, block 0 runs on its own
+    # without the class-major form (form 0) there is nothing to fuse into: the flag is ignored, block 0 runs on its own
     emu_default.check(emu_default.mst_tcn_set_tuning(m._handle, 1 | 32), "tuning")
     assert float((m(x, cnd) - y_ref).abs().max()) <= 4e-2
 
@@ -718,10 +716,9 @@ def test_encoder_rows_kernel_matches_im2col_emulated(emu_default):
         enc.precision = "bf16"
 
 
-def test_encoder_wave_tilings_and_workgroup_orders_match_emulated(emu_default):
-    """bf16 / split-bf16 FXencoder, 128-channel layers: the conv kernel with its waves 2 x 2 (two MFMAs per LDS read) and the weight-major
-    workgroup order (mst_enc_set_schedule) against the 4 x 1 / column-major forms - same operands, same k order per accumulator: the same bits;
-    split-K slices included (short wide layers)."""
+def test_encoder_workgroup_orders_match_emulated(emu_default):
+    """bf16 / split-bf16 FXencoder, 128-channel layers: the weight-major workgroup order (mst_enc_set_schedule bit 0) against the column-major
+    one - same operands, same k order per accumulator: the same bits; split-K slices included (short wide layers)."""
     from music_mixing_style_transfer_amd.networks import FXencoder
     cfg = {"channels": [16, 32, 128, 256], "kernels": [25, 10, 5, 5], "strides": [4, 2, 2, 1], "dilation": [1, 1, 1, 1],
            "bias": True, "norm": "batch", "conv_block": "res", "activation": "relu"}
@@ -735,7 +732,7 @@ def test_encoder_wave_tilings_and_workgroup_orders_match_emulated(emu_default):
         run = enc._get_runner()
         run._ensure(emu_default)
         outs = []
-        for flags in (0, 1, 2, 3):
+        for flags in (0, 1):
             emu_default.check(emu_default.mst_enc_set_schedule(run.handle, flags), "schedule")
             outs.append(enc(x).clone())
         emu_default.check(emu_default.mst_enc_set_schedule(run.handle, 1), "schedule")          # the default
@@ -748,8 +745,9 @@ def test_encoder_wave_tilings_and_workgroup_orders_match_emulated(emu_default):
     assert torch.equal(enc(x), ref32)
     emu_default.check(emu_default.mst_enc_set_schedule(run.handle, 1), "schedule")
     assert float((ref32 - emb).abs().max()) <= 2e-5 * float(emb.abs().max())
-    with pytest.raises(ValueError):
-        emu_default.check(emu_default.mst_enc_set_schedule(run.handle, 64), "schedule")
+    for gone in (64, 2, 3):          # bit 1 selected the 2 x 2 wave tiling, which left the library
+        with pytest.raises(ValueError):
+            emu_default.check(emu_default.mst_enc_set_schedule(run.handle, gone), "schedule")
 
 
 def test_encoder_raw_rows_conv_kernel_emulated(emu_default):

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""A/B of the bf16 TCN block kernel forms on the MI355X (mst_tcn_set_tuning flags 1 / 5 / 21 / 53): the one-tile-per-workgroup kernel
-against the persistent LDS-DMA-fed "duo" kernel (5 tap-major, 21 class-major, 53 = 21 + block 0 inside block 1's launch: the default's bf16 part).  Per-block kernel times from HIP events on the launch stream (mst_tcn_timing_*), the forms
+"""A/B of the bf16 TCN block kernel forms on the MI355X (mst_tcn_set_tuning flags 1 / 21 / 53 / 181): form 0, the tap-major loop for every block,
+against the class-major family (21: two- / four-phase blocks on class-major 256-time tiles, 53 = 21 + block 0 inside block 1's launch, 181 = 53 + the
+whole-sequence tiles and the class-major head of bit 7: the default's bf16 part).  Per-block kernel times from HIP events on the launch stream (mst_tcn_timing_*), the forms
 alternating so that both see the same clock / thermal state; parity of the two forms against each other at full size and against
 the oracle on a short segment.
 
@@ -40,7 +41,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--forms", default="1,5,21,53")
+    ap.add_argument("--forms", default="1,21,53,181")
     ap.add_argument("--segment", type=int, default=131072, help="segment length (the reference's default is 2^19: --segment 524288 --batch 8)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Builds tools/_ab/probe.so (untracked): the product's csrc/ with s_memtime phase stamps patched into ONE wave of ONE workgroup of
-  * tcn_block_bf16_duo_kernel (matrix wave 0, the d = 64 block): probe slots 0 .. 7  (tools/probe_tcn_phases.py --kernel duo)
-  * tcn_block_bf16x3_kernel<2, 4> (wave 0, the d = 64 block):     probe slots 8 .. 15 (tools/probe_tcn_phases.py --kernel x3)
+  * tcn_block_bf16x3_kernel<2, 4> (wave 0, the d = 64 block):           probe slots 8 .. 15  (tools/probe_tcn_phases.py --kernel x3)
+  * enc_conv_nlc_kernel<4> (wave 0, the 2048 -> 2048 encoder layers):  probe slots 16 .. 23 (tools/probe_tcn_phases.py --kernel enc)
 and an extra entry point mst_probe_read().  The product sources carry no probe code.   python tools/build_probe.py"""
 import os
 import subprocess
@@ -35,46 +35,6 @@ def main():
     open(dev, "a").write("\n__device__ long long mst_tcn_probe[32];      // probe build only\n")
     s = patch(s, "struct TcnBlockArgs {", """#define MST_PROBE(k) do { if (probe_on) { const long long now_ = mst_clock(); mst_tcn_probe[k] += now_ - probe_t; probe_t = now_; } } while (0)
 struct TcnBlockArgs {""")
-    # ---- duo kernel, matrix wave 0
-    s = patch(s, """    const unsigned tiles_item = (unsigned)a.tiles_phase * (unsigned)a.tiles_step;
-    for (;;) {
-        const int b = tb, m0 = tm0, phi0 = tphi0;""", """    const unsigned tiles_item = (unsigned)a.tiles_phase * (unsigned)a.tiles_step;
-    const bool probe_on = blockIdx.x == 8 && wv == 0 && lane == 0 && a.d == 64;
-    long long probe_t = mst_clock();
-    for (;;) {
-        MST_PROBE(0);            // loop bookkeeping
-        const int b = tb, m0 = tm0, phi0 = tphi0;""")
-    s = patch(s, """            tcn_reuse_class<P, 15 / NCLS, true, NUMAX>(acc, A0, A1, ring, sm, wst, aoff, NCLS - 1, 0, l16, g);
-        } else {""", """            MST_PROBE(1);        // acc init + ring preload + classes 0 .. NCLS - 2
-            tcn_reuse_class<P, 15 / NCLS, true, NUMAX>(acc, A0, A1, ring, sm, wst, aoff, NCLS - 1, 0, l16, g);
-            MST_PROBE(2);        // the last class
-        } else {""")
-    s = patch(s, """        read_xin(0);
-        mst_dma_wait_barrier<63>();            // (1)""", """        read_xin(0);
-        MST_PROBE(3);            // residual reads issued
-        mst_dma_wait_barrier<63>();            // (1)""")
-    s = patch(s, """        float hs0[NC], hs1[NC];
-#pragma unroll
-        for (int q = 0; q < NC; ++q) hs0[q] = hs1[q] = 0.0f;
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            if (m) {
-                read_xin(1);""", """        MST_PROBE(4);            // barrier 1
-        float hs0[NC], hs1[NC];
-#pragma unroll
-        for (int q = 0; q < NC; ++q) hs0[q] = hs1[q] = 0.0f;
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            if (m) {
-                read_xin(1);""")
-    s = patch(s, """        } else {
-            mst_dma_wait_barrier<63>();          // (2) the transposed output tile is complete: the loader waves store it
-        }""", """        } else {
-            MST_PROBE(5);        // epilogue arithmetic + LDS writes
-            mst_dma_wait_barrier<63>();          // (2) the transposed output tile is complete: the loader waves store it
-            MST_PROBE(6);        // barrier 2
-            if (probe_on) mst_tcn_probe[7] += 1;
-        }""")
     # ---- split-bf16 one-tile kernel
     s = patch(s, """    const float *xb = (const float *)a.x + (size_t)b * a.Lp * 128;
     float *yb = (float *)a.y + (size_t)b * a.Lp * 128;
@@ -133,7 +93,7 @@ struct TcnBlockArgs {""")
     s = open(p).read()
     s = patch(s, "struct EncNlcArgs {", """#define MST_EPROBE(k) do { if (eprobe_on) { const long long now_ = mst_clock(); mst_tcn_probe[k] += now_ - eprobe_t; eprobe_t = now_; } } while (0)
 struct EncNlcArgs {""")
-    NB, NE = "void enc_conv_nlc_kernel(EncNlcArgs a) {", "// The 128-channel x 128-column tile with its four waves 2 x 2"
+    NB, NE = "void enc_conv_nlc_kernel(EncNlcArgs a) {", "struct EncTapsArgs {"
     s = patch(s, """    if (kc_lo < kc_hi) {
         stab_entry(kc_lo);
         fetch(kc_lo);

@@ -26,8 +26,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--tuning", type=int, default=None, help="mst_tcn_set_tuning flags for every model (e.g. 85 = default + bit 6)")
     ap.add_argument("--only", default=None, help="restrict the sweep to one precision")
-    ap.add_argument("--fuse0", action="store_true", help="bf16 cases only: also run with mst_tcn_set_tuning bit 5 (block 0 computed by block 1's loader "
-                                                          "waves) and require the same bits")
+    ap.add_argument("--fuse0", action="store_true", help="bf16 cases only: also run with mst_tcn_set_tuning bit 5 (block 0 computed in block 1's "
+                                                          "staging) and require the same bits")
     args = ap.parse_args()
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     from emu_binding import bind_emulator

@@ -30,7 +30,7 @@ python tools/rocprof_summary.py "$(find $O/prof_fx -name '*.db' | head -1)" "too
 if [ -n "$WITH_PMC" ]; then
 FD=$(dirname $(find $O/pmc_fetch -name "*counter_collection.csv" | head -1)); WD=$(dirname $(find $O/pmc_write -name "*counter_collection.csv" | head -1))
 for d in $FD $WD; do f=$(ls $d/*counter_collection.csv | head -1); [ "$f" != "$d/pmc_counter_collection.csv" ] && cp $f $d/pmc_counter_collection.csv; done
-python tools/pmc_traffic.py $FD $WD tcn_block_bf16_duo_kernel $O/r05_tcn_block_bf16_traffic.json > $O/pmc_traffic.log 2>&1
+python tools/pmc_traffic.py $FD $WD tcn_block_bf16_kernel $O/r05_tcn_block_bf16_traffic.json > $O/pmc_traffic.log 2>&1
 N=4 bash tools/gpu_fx_pmc.sh > $O/fx_pmc.log 2>&1; cp gpurun_out/fx_chain_traffic.json $O/r05_fx_chain_traffic.json
 fi
 find $O -name "*.db" -delete; rm -rf $O/pmc_fetch $O/pmc_write $O/prof_bf16 $O/prof_x3 $O/prof_fx; ls $O

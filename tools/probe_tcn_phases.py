@@ -1,9 +1,9 @@
 #!/usr/bin/env python
-"""Phase clocks of the dominant kernel (tcn_block_bf16_duo_kernel<4>, the d = 64 block of the default TCN at 32 x 131072; --kernel x3: the
-split-bf16 tcn_block_bf16x3_kernel<2, 4>): a PROBE BUILD of the library (tools/_ab/probe.so, built by tools/build_probe.py: csrc/ with s_memtime
-stamps patched into one wave of one workgroup; tools/_ab is untracked) accumulates the shader clocks that wave spends per tile in: [0] loop bookkeeping, [1] accumulator init + ring preload +
-classes 0 .. 2, [2] the last class, [3] issuing the residual reads, [4] barrier 1, [5] epilogue arithmetic + LDS writes, [6] barrier 2; [7] tiles.
-    python tools/probe_tcn_phases.py [--forwards 5]"""
+"""Phase clocks of one kernel at 32 x 131072 - the split-bf16 tcn_block_bf16x3_kernel<2, 4> on the d = 64 block of the default TCN (--kernel x3)
+or the FXencoder's enc_conv_nlc_kernel<4> on its 2048 -> 2048 layers (--kernel enc): a PROBE BUILD of the library (tools/_ab/probe.so, built by
+tools/build_probe.py: csrc/ with s_memtime stamps patched into one wave of one workgroup; tools/_ab is untracked) accumulates the shader clocks that
+wave spends per tile in each phase of the kernel (the names are printed).
+    python tools/probe_tcn_phases.py [--kernel x3] [--forwards 5]"""
 import argparse
 import ctypes as C
 import os
@@ -18,7 +18,7 @@ sys.path.insert(0, REPO)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--forwards", type=int, default=5)
-    ap.add_argument("--kernel", default="duo", choices=["duo", "x3", "enc"])
+    ap.add_argument("--kernel", default="x3", choices=["x3", "enc"])
     ap.add_argument("--lib", default=os.path.join(REPO, "tools", "_ab", "probe.so"))
     args = ap.parse_args()
     import yaml
@@ -59,7 +59,6 @@ def main():
     torch.cuda.synchronize()
     assert rd(out, 0) == 0
     v = [int(t) for t in out]
-    names = ["loop bookkeeping", "acc init + ring preload + classes 0..2", "last class", "residual reads issued", "barrier 1", "epilogue arithmetic + LDS writes", "barrier 2"]
     if args.kernel == "x3":          # tcn_block_bf16x3_kernel<2, 4>: one 128-time tile per workgroup, two workgroups per CU
         v = v[8:]
         names = ["staging (loads, hi / lo split, LDS writes)", "barrier", "main loop (three MFMAs per product)", "barrier", "LeakyReLU / FiLM + transposed LDS writes", "barrier",
