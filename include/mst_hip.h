@@ -123,7 +123,7 @@ int mst_tcn_forward_blocks(MstTcn *tcn, const float *x_dev, float *act_dev, int 
  *                                                                  1 and 3 rejected (MST_ERR_ARG)
  *                                  bit 3                  0        rejected (MST_ERR_ARG)
  *                                  bit 4                  1        required with form 2 (form 2 without it: MST_ERR_ARG); ignored with form 0
- *                                  bit 5                  1        bf16, form 2: block 0 inside the d = 2 block's launch      =       separate block-0 kernel = probes, other precisions, short segments
+ *                                  bit 5                  1        bf16, form 2: block 0 inside the d = 2 block's launch      =       separate block-0 kernel = block 0's own probe, other precisions, nets it cannot apply to
  *                                  bit 6                  1        bf16x3: class-major loop in the eight-phase half kernel    ~       other side of a GPU test
  *                                  bit 7                  1        bf16, form 2: whole-sequence 256-time tiles and the        =/~     off = those blocks on the general tilings and the
  *                                                                  class-major fused head of a four-phase last block                  tap-major head: the other side of the tests
@@ -142,8 +142,8 @@ int mst_tcn_forward_blocks(MstTcn *tcn, const float *x_dev, float *act_dev, int 
  *   bf16 form 2: the two- and four-phase blocks that are not the last one run tcn_block_bf16_kernel<P, false, 8, 2> (one 256-time tile per
  *     workgroup, two workgroups per CU, B fragments reused across the taps of a class); every other block - P = 1 (odd dilations), the 128-time
  *     and sixteen-phase tilings - runs what form 0 runs, bit 7's forms aside.  The two forms agree to fp32 accumulation rounding.
- *   bit 5: applies only when block 1 is the d = 2 block on two-phase tiles (>= 128 steps per phase) and not the last block; otherwise the
- *     separate block-0 kernel runs - mst_tcn_get_tuning reports which happened.  Same bits either way.
+ *   bit 5: applies only when block 1 is the d = 2 block (two-phase tiles at every segment length) of a net of more than two blocks and at
+ *     least two blocks run; otherwise the separate block-0 kernel runs - mst_tcn_get_tuning reports which happened.  Same bits either way.
  *   bit 7: a block whose phase sequences are EXACTLY one 256-time tile (L = 64 d, 32 d or 16 d: d = 2048 / 4096 / 8192 at L = 131072) runs the
  *     unrolled forms <4 | 8 | 16, ., 8, 1> (no all-padding (column tile, tap) pair; the sixteen-phase form carries the fused head): the
  *     four-phase form is bit-identical to bit 7 off, the other two one bf16 ulp away on the activation.  A four-phase LAST block (segments of

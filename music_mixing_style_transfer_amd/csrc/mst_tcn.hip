@@ -15,6 +15,17 @@ struct MstTcnBlock {
     bool loaded = false;
 };
 
+// kernel forms: the mst_tcn_set_tuning flags (include/mst_hip.h; measured at 32 x 131072: bit 0 5.13 against 5.45 ms per bf16x3 launch,
+// bit 5 -0.2 ms per bf16 forward, bit 6 572 against 566 bf16x3 segments/s - profiles/r05_x3_ab_bit6_53_117.jsonl)
+struct TcnTuning {
+    int flags;
+    bool x3_small_tiles() const { return flags & 1; }               // bf16x3: 128-time tiles of <= 2 phases, two workgroups per CU
+    bool bf16_cm() const { return ((flags >> 1) & 3) == 2; }        // bf16 form 2: two- / four-phase blocks on class-major 256-time tiles
+    bool bf16_fuse0() const { return bf16_cm() && (flags & 32); }   // bf16: block 0 inside the d = 2 block's launch
+    bool x3_half_cm() const { return flags & 64; }                  // bf16x3: class-major loop in the eight-phase half-tile kernel
+    bool bf16_whole() const { return bf16_cm() && (flags & 128); }  // bf16: whole-sequence 256-time tiles, class-major head of a four-phase last block
+};
+
 constexpr int TCN_FILM_ROWS0 = 64;      // FiLM rows reserved at create time (14 blocks x 64 rows x 256 floats = 0.9 MB)
 struct MstTcn {
     MstTcnDesc d;
@@ -29,14 +40,7 @@ struct MstTcn {
     float *out_w = nullptr, *out_b = nullptr;
     bool out_loaded = false;
     void *zero_row = nullptr;     // 1 KB of zeros: what the block kernels stage for time steps outside the segment
-    // kernel forms: the mst_tcn_set_tuning flags as set (include/mst_hip.h; measured at 32 x 131072: bit 0 5.13 against 5.45 ms per bf16x3 launch,
-    // bit 5 -0.2 ms per bf16 forward, bit 6 572 against 566 bf16x3 segments/s - profiles/r05_x3_ab_bit6_53_117.jsonl)
-    int tuning = 245;
-    bool x3_small_tiles() const { return tuning & 1; }              // bf16x3: 128-time tiles of <= 2 phases, two workgroups per CU
-    bool bf16_cm() const { return ((tuning >> 1) & 3) == 2; }       // bf16 form 2: two- / four-phase blocks on class-major 256-time tiles
-    bool bf16_fuse0() const { return bf16_cm() && (tuning & 32); }  // bf16: block 0 inside the d = 2 block's launch
-    bool x3_half_cm() const { return tuning & 64; }                 // bf16x3: class-major loop in the eight-phase half-tile kernel
-    bool bf16_whole() const { return bf16_cm() && (tuning & 128); } // bf16: whole-sequence 256-time tiles, class-major head of a four-phase last block
+    int tuning = 245;             // TcnTuning flags (mst_tcn_set_tuning)
     int last_fused0 = 0;          // whether the last forward of this handle really ran block 0 inside block 1's launch (mst_tcn_get_tuning)
     std::vector<hipEvent_t> ev;   // timing hook: (nblocks + 2) events per recorded forward
     int ev_max = 0, ev_used = 0;
@@ -121,54 +125,36 @@ extern "C" int mst_tcn_load_block(MstTcn *t, int n, const float *conv_w, const f
     std::vector<float> scale, shift;
     bn_fold(bn_weight, bn_bias, bn_mean, bn_var, bn_eps, C, scale, shift);
     MstTcnBlock &b = t->blk[n];
+    auto W = [&](int co, int ci, int j) { return conv_w[((size_t)co * cin + ci) * K + j] * scale[co]; };
+    int rc;
     if (t->generic) {
-        int rc;
         MstEncConv &c = t->gconv[n];
         if ((rc = pack_conv_f32(c, conv_w, scale))) return rc;
         std::vector<float> sh((size_t)((C + 32 * c.mw - 1) / (32 * c.mw)) * 32 * c.mw, 0.0f);
         for (int co = 0; co < C; ++co) sh[co] = shift[co];
         if ((rc = upload(&c.shift, sh))) return rc;
-        std::vector<float> res(res_w, res_w + C);
-        if ((rc = upload(&b.res, res))) return rc;
-        const size_t fwn = (size_t)2 * C * t->d.cond_dim;
-        MST_HIP_TRY(hipMemcpy(t->film_w + (size_t)n * fwn, film_w, fwn * sizeof(float), hipMemcpyHostToDevice));
-        MST_HIP_TRY(hipMemcpy(t->film_b + (size_t)n * 2 * C, film_b, 2 * C * sizeof(float), hipMemcpyHostToDevice));
-        c.loaded = b.loaded = true;
-        return MST_OK;
-    }
-    auto W = [&](int co, int ci, int j) { return conv_w[((size_t)co * cin + ci) * K + j] * scale[co]; };
-    int rc;
-    if (n == 0) {
+        c.loaded = true;
+    } else if (n == 0) {
         std::vector<float> w0((size_t)cin * K * C);
         for (int ci = 0; ci < cin; ++ci)
             for (int j = 0; j < K; ++j)
                 for (int co = 0; co < C; ++co) w0[((size_t)ci * K + j) * C + co] = W(co, ci, j);
         if ((rc = upload(&b.w_f32, w0))) return rc;
-        if (cin == 2 && K == 15) {        // bf16 A fragments of the matrix-core block-0 kernel: [s][wave][lane][e], k = ci * 15 + j
-            std::vector<__bf16> wb((size_t)2 * 4 * 64 * 8);
-            for (int sI = 0; sI < 2; ++sI)
-                for (int w = 0; w < 4; ++w)
-                    for (int l = 0; l < 64; ++l)
-                        for (int e = 0; e < 8; ++e) {
-                            const int k = 16 * sI + 8 * (l >> 5) + e;
-                            wb[(((size_t)sI * 4 + w) * 64 + l) * 8 + e] = k < 30 ? (__bf16)W(32 * w + (l & 31), k / 15, k % 15) : (__bf16)0.0f;
-                        }
-            if ((rc = upload((__bf16 **)&b.w_bf16, wb))) return rc;
-        }
-    } else {
-        // bf16 A fragments of v_mfma_f32_16x16x32_bf16: [ks = j*4 + kk][row tile m][wave][lane][e]
-        std::vector<__bf16> wb((size_t)120 * 4 * 64 * 8);
-        for (int j = 0; j < K; ++j)
-            for (int kk = 0; kk < 4; ++kk)
-                for (int m = 0; m < 2; ++m)
-                    for (int w = 0; w < 4; ++w)
-                        for (int l = 0; l < 64; ++l)
-                            for (int e = 0; e < 8; ++e)
-                                wb[(((((size_t)(j * 4 + kk) * 2 + m) * 4 + w) * 64 + l) * 8) + e] =
-                                    (__bf16)W(32 * w + 16 * m + (l & 15), 32 * kk + 8 * (l >> 4) + e, j);
+        // bf16 A fragments of the matrix-core block-0 kernel: [s][wave][lane][e], k = ci * 15 + j
+        std::vector<__bf16> wb((size_t)2 * 4 * 64 * 8);
+        for (int sI = 0; sI < 2; ++sI)
+            for (int w = 0; w < 4; ++w)
+                for (int l = 0; l < 64; ++l)
+                    for (int e = 0; e < 8; ++e) {
+                        const int k = 16 * sI + 8 * (l >> 5) + e;
+                        wb[(((size_t)sI * 4 + w) * 64 + l) * 8 + e] = k < 30 ? (__bf16)W(32 * w + (l & 31), k / 15, k % 15) : (__bf16)0.0f;
+                    }
         if ((rc = upload((__bf16 **)&b.w_bf16, wb))) return rc;
-        // bf16x3 mode: the same fragment image twice, W'_hi = bf16(W') and W'_lo = bf16(W' - W'_hi)
-        std::vector<__bf16> wx((size_t)2 * 120 * 4 * 64 * 8);
+    } else {
+        // bf16 A fragments of v_mfma_f32_16x16x32_bf16: [ks = j*4 + kk][row tile m][wave][lane][e]; bf16x3 mode: the same fragment image twice,
+        // W'_hi = bf16(W') and W'_lo = bf16(W' - W'_hi)
+        const size_t image = (size_t)120 * 4 * 64 * 8;
+        std::vector<__bf16> wb(image), wx(2 * image);
         for (int j = 0; j < K; ++j)
             for (int kk = 0; kk < 4; ++kk)
                 for (int m = 0; m < 2; ++m)
@@ -178,9 +164,10 @@ extern "C" int mst_tcn_load_block(MstTcn *t, int n, const float *conv_w, const f
                                 const float v = W(32 * w + 16 * m + (l & 15), 32 * kk + 8 * (l >> 4) + e, j);
                                 const __bf16 hi = (__bf16)v;
                                 const size_t idx = (((((size_t)(j * 4 + kk) * 2 + m) * 4 + w) * 64 + l) * 8) + e;
-                                wx[idx] = hi;
-                                wx[(size_t)120 * 4 * 64 * 8 + idx] = (__bf16)(v - (float)hi);
+                                wb[idx] = wx[idx] = hi;
+                                wx[image + idx] = (__bf16)(v - (float)hi);
                             }
+        if ((rc = upload((__bf16 **)&b.w_bf16, wb))) return rc;
         if ((rc = upload((__bf16 **)&b.w_x3, wx))) return rc;
         // fp32 A fragments of v_mfma_f32_32x32x2_f32: [j][chunk c][ksg][wave][lane][i]
         std::vector<float> wf((size_t)K * 4 * 4 * 4 * 64 * 4);
@@ -194,7 +181,7 @@ extern "C" int mst_tcn_load_block(MstTcn *t, int n, const float *conv_w, const f
                                     W(32 * w + (l & 31), 32 * c + 2 * (4 * ksg + i) + (l >> 5), j);
         if ((rc = upload(&b.w_f32, wf))) return rc;
     }
-    if ((rc = upload(&b.shift, shift))) return rc;
+    if (!t->generic && (rc = upload(&b.shift, shift))) return rc;      // (the generic conv keeps its shift, padded, with its packed weights)
     std::vector<float> res(res_w, res_w + C);
     if ((rc = upload(&b.res, res))) return rc;
     const size_t fwn = (size_t)2 * C * t->d.cond_dim;
@@ -260,158 +247,165 @@ namespace {
 
 size_t tcn_elem(int precision) { return precision == MST_PREC_BF16 ? 2 : 4; }      // bf16x3 keeps fp32 activations in HBM
 
-// bf16 mode, tile forms that tcn_run picks beside the phase count (launch_block's bf16_tile)
-enum { TILE_DEFAULT = 0,             // 256-time tiles of P phases (128-time at P = 8)
-       TILE_128_FOUR_PHASES = 1,     // 17 ... 32 steps per phase: 128-time tiles of four phases instead of eight, three workgroups per CU
-       TILE_WHOLE_256 = 3 };         // a phase sequence is exactly one 256-time tile (64 / 32 / 16 steps at 4 / 8 / 16 phases): unrolled loop, trimmed halo
-// phases per tile: P | d.  P = 4 with 256-time tiles (78 KB of LDS, 2 workgroups per CU) whenever a tile's 64 steps
-// fit the segment; for larger dilations P = 8 with 128-time tiles (16 steps per tile, 61 KB, still 2 per CU); P = 16
-// (256-time tiles, 16 steps per tile) only for segments with fewer than 16 steps per phase.
-int choose_phases(int d, int L, int precision) {
-    int P = (d % 4 == 0) ? 4 : (d % 2 == 0 ? 2 : 1);
-    const long nsteps = ((long)L + d - 1) / d;
-    if (precision == MST_PREC_BF16X3) {    // two LDS tiles (hi, lo): 256-time tiles up to P = 4, 128-time tiles of 8 phases for large dilations
-        if (P == 4 && d % 8 == 0 && 256 / P > nsteps) P = 8;
-        return P;
-    }
-    if (precision == MST_PREC_BF16X3 + 100) {   // bf16x3 with small tiles: 2 phases wherever 64 steps fit the segment
-        int Q = (d % 2 == 0) ? 2 : 1;
-        if (128 / Q <= nsteps) return Q;
-        return choose_phases(d, L, MST_PREC_BF16X3);
-    }
-    if (precision != MST_PREC_BF16) {      // fp32 kernel: 256-time tiles only (its LDS tile is a 32-channel chunk)
-        while (P < 16 && d % (2 * P) == 0 && 256 / P > nsteps) P *= 2;
-        return P;
-    }
-    while (P < 8 && d % (2 * P) == 0 && 256 / P > nsteps) P *= 2;
-    if (P == 8 && d % 16 == 0 && nsteps < 16) P = 16;     // very short segments: 16-step tiles of 16 phases
-    return P;
-}
+// ---- the launch plan of one dense block (blocks >= 1): everything that is decided per block, decided once, by tcn_plan_block ----
+enum TcnFamily { TCN_BF16, TCN_BF16X3, TCN_BF16X3_HALF, TCN_F32 };      // tcn_block_bf16_kernel, _bf16x3_kernel, _bf16x3_half_kernel, _f32_kernel
+struct TcnBlockPlan {
+    TcnFamily family;
+    int P;            // phases per tile, P | d
+    int tile;         // output times per tile, 256 or 128 (the kernels' NQ = tile / 32): a tile is P phases x tile / P steps
+    int form;         // bf16, the kernel's WHOLE: 0 tap-major loop, 1 unrolled loop of a tile that spans its whole phase sequence, 2 class-major
+                      // loop; bf16x3 half-tile kernel: 1 = class-major loop (CM)
+    bool head;        // the output head runs in this block's epilogue (no tcn_output_kernel)
+    bool block0;      // bf16: block 0 is computed in this block's staging (FUSE0; no block-0 kernel)
+    int tiles_phase;  // d / P
+    int tiles_step;   // ceil(steps per phase / steps per tile)
+    long grid;        // B * tiles_phase * tiles_step workgroups
+    int xcd_tiles;    // XCD-aware tile order (TcnBlockArgs::xcd_tiles): measured read traffic 1.38 -> 1.20 GB per bf16 launch at P = 4 (1.07 algorithmic)
+};
 
-template <int P> int launch_block(const MstTcn &t, int precision, const TcnBlockArgs &a0, int grid, void *stream, int x3_small, int bf16_tile) {
-    TcnBlockArgs a = a0;
-    if constexpr (P == 4) {
-        // (the same 128-time form for EVERY block - three workgroups per CU - measured 1.53-1.58 ms per launch against 1.48-1.53 for round 3's
-        //  persistent 256-time kernel: it only wins where the eight-phase tiles' halo is the alternative)
-        if (precision == MST_PREC_BF16 && bf16_tile == TILE_128_FOUR_PHASES) {          // 128-time tiles of 4 phases (one-tile kernel, three workgroups per CU)
-            const long nsteps = ((long)a.L + a.d - 1) / a.d;
-            a.tiles_step = (int)((nsteps + 128 / P - 1) / (128 / P));
-            const long g2 = (long)a.B * a.tiles_phase * a.tiles_step;
-            if (g2 % 8 == 0) a.xcd_tiles = (int)(g2 / 8);
-            const bool whole = a.tiles_step == 1 && nsteps == 128 / P;          // every tile spans its whole phase sequence: unrolled class-major loop
-            if (a.y_out && whole)
-                MST_LAUNCH((tcn_block_bf16_kernel<P, true, 4, 1>), dim3((unsigned)g2), dim3(256), stream, a);
-            else if (a.y_out)
-                MST_LAUNCH((tcn_block_bf16_kernel<P, true, 4>), dim3((unsigned)g2), dim3(256), stream, a);
-            else if (whole)
-                MST_LAUNCH((tcn_block_bf16_kernel<P, false, 4, 1>), dim3((unsigned)g2), dim3(256), stream, a);
-            else
-                MST_LAUNCH((tcn_block_bf16_kernel<P, false, 4>), dim3((unsigned)g2), dim3(256), stream, a);
-            MST_CHECK_LAUNCH("tcn_block_bf16_kernel");
-            return MST_OK;
-        }
-    }
-    if constexpr (P == 16 || P == 8 || P == 4) {
-        if (precision == MST_PREC_BF16 && bf16_tile == TILE_WHOLE_256) {          // one 256-time tile = the whole phase sequence (tcn_run checked the shape)
-            a.tiles_step = 1;
-            grid = (int)((long)a.B * a.tiles_phase);
-            if (grid % 8 == 0) a.xcd_tiles = grid / 8;
-            if constexpr (P == 16) {
-                if (a.y_out) MST_LAUNCH((tcn_block_bf16_kernel<P, true, 8, 1>), dim3(grid), dim3(256), stream, a);
-                else MST_LAUNCH((tcn_block_bf16_kernel<P, false, 8, 1>), dim3(grid), dim3(256), stream, a);
-            } else {
-                if (a.y_out) return fail(MST_ERR_STATE, "tcn_block_bf16_kernel: the fused head exists for the sixteen-phase whole-sequence tile only");
-                MST_LAUNCH((tcn_block_bf16_kernel<P, false, 8, 1>), dim3(grid), dim3(256), stream, a);
-            }
-            MST_CHECK_LAUNCH("tcn_block_bf16_kernel");
-            return MST_OK;
-        }
-    }
-    if (precision == MST_PREC_BF16 && t.bf16_cm()) {
-        // form 2: the two- and four-phase blocks on 256-time class-major tiles, two workgroups per CU (round 6: 1.31 ms per launch against 1.40
-        // for round 3's persistent kernel with the same loop); P = 1 and the eight-phase blocks run the general forms below
-        if constexpr (P == 4) {
-            if (!a.y_out || t.bf16_whole()) {          // the last block of a long segment (fused head): class-major with bit 7, else tap-major below
-                if (grid % 8 == 0) a.xcd_tiles = grid / 8;
-                if (a.y_out) MST_LAUNCH((tcn_block_bf16_kernel<P, true, 8, 2>), dim3(grid), dim3(256), stream, a);
-                else MST_LAUNCH((tcn_block_bf16_kernel<P, false, 8, 2>), dim3(grid), dim3(256), stream, a);
-                MST_CHECK_LAUNCH("tcn_block_bf16_kernel");
-                return MST_OK;
-            }
-        }
-        if constexpr (P == 2) {
-            if (!a.y_out) {          // the d = 2 block; with bit 5 it computes block 0 in its staging (a two-phase last block runs tap-major below)
-                if (grid % 8 == 0) a.xcd_tiles = grid / 8;
-                if (a.x0) MST_LAUNCH((tcn_block_bf16_kernel<P, false, 8, 2, true>), dim3(grid), dim3(256), stream, a);
-                else MST_LAUNCH((tcn_block_bf16_kernel<P, false, 8, 2>), dim3(grid), dim3(256), stream, a);
-                MST_CHECK_LAUNCH("tcn_block_bf16_kernel");
-                return MST_OK;
-            }
-        }
-    }
-    if (precision == MST_PREC_BF16X3) {
-        if constexpr (P <= 2) {
-            if (x3_small) {          // 128-time tiles: 2 x 39 KB of LDS, two workgroups (8 waves) per CU
-                const long nsteps = ((long)a.L + a.d - 1) / a.d;
-                a.tiles_step = (int)((nsteps + 128 / P - 1) / (128 / P));
-                const long g2 = (long)a.B * a.tiles_phase * a.tiles_step;
-                if (g2 % 8 == 0) a.xcd_tiles = (int)(g2 / 8);
-                MST_LAUNCH((tcn_block_bf16x3_kernel<P, 4>), dim3((unsigned)g2), dim3(256), stream, a);
-                MST_CHECK_LAUNCH("tcn_block_bf16x3_kernel");
-                return MST_OK;
-            }
-        }
-        if constexpr (P <= 8) {
-            constexpr int NQ = P == 8 ? 4 : 8;
-            const long nsteps = ((long)a.L + a.d - 1) / a.d;
-            a.tiles_step = (int)((nsteps + (32 * NQ) / P - 1) / ((32 * NQ) / P));
-            const long g2 = (long)a.B * a.tiles_phase * a.tiles_step;
-            if (g2 % 8 == 0) a.xcd_tiles = (int)(g2 / 8);
-            if constexpr (P == 8) {    // 8-phase tiles: the input staged in two halves of 64 channels (60 KB of LDS, two workgroups per CU)
-                if (t.x3_half_cm())
-                    MST_LAUNCH((tcn_block_bf16x3_half_kernel<P, NQ, true>), dim3((unsigned)g2), dim3(256), stream, a);
-                else
-                    MST_LAUNCH((tcn_block_bf16x3_half_kernel<P, NQ>), dim3((unsigned)g2), dim3(256), stream, a);
-            } else
-            MST_LAUNCH((tcn_block_bf16x3_kernel<P, NQ>), dim3((unsigned)g2), dim3(256), stream, a);
-            MST_CHECK_LAUNCH("tcn_block_bf16x3_kernel");
-            return MST_OK;
+// `head`: the block is the last one of a forward (not of a probe); `behind_block0`: it is block 1 of a net that goes on behind it and whose
+// block 0 has dilation 1 - the only place block 0 can move into.
+TcnBlockPlan tcn_plan_block(int tuning, int precision, int d, int L, int B, bool head, bool behind_block0) {
+    const TcnTuning f{tuning};
+    const long nsteps = ((long)L + d - 1) / d;      // steps per phase
+    TcnBlockPlan p = {};
+    // phases per tile: P | d.  P = 4 with 256-time tiles (bf16: 78 KB of LDS, 2 workgroups per CU) whenever a tile's 64 steps fit the segment
+    int P = (d % 4 == 0) ? 4 : (d % 2 == 0 ? 2 : 1);
+    p.tile = 256;
+    if (precision == MST_PREC_F32) {
+        // fp32 kernel: 256-time tiles only (its LDS tile is a 32-channel chunk), up to 16 phases; the separate head
+        p.family = TCN_F32;
+        while (P < 16 && d % (2 * P) == 0 && 256 / P > nsteps) P *= 2;
+    } else if (precision == MST_PREC_BF16X3) {
+        // two LDS tiles (hi, lo).  The head is fused: the kernels exist for up to 8 phases, which is every dilation here
+        p.head = head;
+        const int Q = std::min(P, 2);
+        if (f.x3_small_tiles() && 128 / Q <= nsteps) P = Q;       // bit 0: 2 phases wherever a 128-time tile's 64 steps fit the segment
+        else if (P == 4 && d % 8 == 0 && nsteps < 64) P = 8;       // large dilations: 8 phases
+        if (P == 8) {
+            // the input staged in two halves of 64 channels, 128-time tiles (60 KB of LDS, two workgroups per CU)
+            p.family = TCN_BF16X3_HALF;
+            p.tile = 128;
+            p.form = f.x3_half_cm() ? 1 : 0;
         } else {
-            return fail(MST_ERR_UNSUPPORTED, "tcn_block_bf16x3_kernel: no 16-phase form");
-        }
-    }
-    if (precision == MST_PREC_BF16) {
-        // XCD-aware tile order: measured read traffic 1.38 -> 1.20 GB per launch at P = 4 (1.07 algorithmic)
-        constexpr int xcd_on = 1;
-        if constexpr (P == 8) {
-            // P = 8 tiles of 256 times need 94 KB of LDS (one workgroup per CU); 128-time tiles (61 KB) keep two resident:
-            // measured 1.98 -> 1.70 ms for the d = 4096 block at L = 131072
-            const long nsteps = ((long)a.L + a.d - 1) / a.d;
-            a.tiles_step = (int)((nsteps + 128 / P - 1) / (128 / P));
-            const long g2 = (long)a.B * a.tiles_phase * a.tiles_step;
-            if (xcd_on && g2 % 8 == 0) a.xcd_tiles = (int)(g2 / 8);
-            const bool whole = a.tiles_step == 1 && nsteps == 128 / P;
-            if (a.y_out && whole)
-                MST_LAUNCH((tcn_block_bf16_kernel<P, true, 4, 1>), dim3((unsigned)g2), dim3(256), stream, a);
-            else if (a.y_out)
-                MST_LAUNCH((tcn_block_bf16_kernel<P, true, 4>), dim3((unsigned)g2), dim3(256), stream, a);
-            else if (whole)
-                MST_LAUNCH((tcn_block_bf16_kernel<P, false, 4, 1>), dim3((unsigned)g2), dim3(256), stream, a);
-            else
-                MST_LAUNCH((tcn_block_bf16_kernel<P, false, 4>), dim3((unsigned)g2), dim3(256), stream, a);
-        } else {
-            if (xcd_on && grid % 8 == 0) a.xcd_tiles = grid / 8;
-            if (a.y_out)
-                MST_LAUNCH((tcn_block_bf16_kernel<P, true, 8>), dim3(grid), dim3(256), stream, a);
-            else
-                MST_LAUNCH((tcn_block_bf16_kernel<P, false, 8>), dim3(grid), dim3(256), stream, a);
+            // 256-time tiles up to P = 4; bit 0: every block of <= 2 phases on 128-time tiles (2 x 39 KB of LDS, two workgroups = 8 waves per CU)
+            p.family = TCN_BF16X3;
+            if (f.x3_small_tiles() && P <= 2) p.tile = 128;
         }
     } else {
-        if (grid % 8 == 0) a.xcd_tiles = grid / 8;
-        MST_LAUNCH((tcn_block_f32_kernel<P>), dim3(grid), dim3(256), stream, a);
+        p.family = TCN_BF16;
+        p.head = head;
+        // for larger dilations P = 8; P = 16 (256-time tiles, 16 steps per tile) only for segments with fewer than 16 steps per phase
+        while (P < 8 && d % (2 * P) == 0 && 256 / P > nsteps) P *= 2;
+        if (P == 8 && d % 16 == 0 && nsteps < 16) P = 16;
+        if (P == 8) {
+            // P = 8 tiles of 256 times need 94 KB of LDS (one workgroup per CU); 128-time tiles (16 steps per tile, 61 KB) keep two resident:
+            // measured 1.98 -> 1.70 ms for the d = 4096 block at L = 131072
+            p.tile = 128;
+            // 17 ... 32 steps per phase (d = 4096 at L = 131072): 128-time tiles of FOUR phases x 32 steps (184 rows staged per 128 outputs, three
+            // workgroups per CU) instead of eight phases x 16 steps (240 rows, two workgroups per CU).  (The same 128-time form for EVERY block
+            // measured 1.53-1.58 ms per launch against 1.48-1.53 for round 3's persistent 256-time kernel: it only wins where the eight-phase
+            // tiles' halo is the alternative)
+            if (nsteps > 16 && nsteps <= 32) P = 4;
+        }
+        // bit 7, a block whose phase sequences are EXACTLY one 256-time tile - sixteen phases x 16 steps (d = 8192 at L = 131072, the last block),
+        // eight x 32 (d = 4096), four x 64 (d = 2048): the unrolled class-major loop without the all-padding (column tile, tap) pairs, an LDS image
+        // without the halo steps no live row window reaches (256 / 272 / 280 rows), two workgroups per CU.  With the fused head only the
+        // sixteen-phase form fits 256 registers (248; the other two would spill)
+        const int Pw = nsteps == 16 ? 16 : (nsteps == 32 ? 8 : (nsteps == 64 ? 4 : 0));
+        if (f.bf16_whole() && Pw && d % Pw == 0 && (long)L == nsteps * d && (!head || Pw == 16)) {
+            P = Pw;
+            p.tile = 256;
+            p.form = 1;
+        } else if (p.tile == 128) {
+            p.form = nsteps == 128 / P ? 1 : 0;      // the one tile of a phase spans its whole sequence: unrolled class-major loop
+        } else if (f.bf16_cm() && ((P == 4 && (!head || f.bf16_whole())) || (P == 2 && !head))) {
+            // form 2: the two- and four-phase blocks on 256-time class-major tiles, two workgroups per CU (round 6: 1.31 ms per launch against 1.40
+            // for round 3's persistent kernel with the same loop); P = 1, sixteen phases and a two-phase last block run the tap-major loop, and
+            // so does a four-phase last block (the head of a long segment) without bit 7
+            p.form = 2;
+            p.block0 = P == 2 && d == 2 && behind_block0 && f.bf16_fuse0();      // bit 5: the d = 2 block computes block 0 in its staging
+        }
     }
-    MST_CHECK_LAUNCH("tcn_block_kernel");
-    return MST_OK;
+    p.P = P;
+    p.tiles_phase = d / P;
+    const int tile_steps = p.tile / P;
+    p.tiles_step = (int)((nsteps + tile_steps - 1) / tile_steps);
+    p.grid = (long)B * p.tiles_phase * p.tiles_step;
+    p.xcd_tiles = p.grid % 8 == 0 ? (int)(p.grid / 8) : 0;
+    return p;
+}
+
+// every instantiation of the four block kernels, once, keyed by the plan fields that are template arguments
+struct TcnBlockKernel {
+    TcnFamily family;
+    int P, tile, form;
+    bool head, block0;      // (bf16 only: the other kernels test TcnBlockArgs::y_out)
+    void (*kernel)(TcnBlockArgs);
+    const char *name;
+};
+#define TCN_BF16_KERNEL(P, HEAD, NQ, WHOLE, FUSE0) \
+    {TCN_BF16, P, 32 * NQ, WHOLE, HEAD, FUSE0, tcn_block_bf16_kernel<P, HEAD, NQ, WHOLE, FUSE0>, "tcn_block_bf16_kernel"}
+#define TCN_X3_KERNEL(P, NQ) {TCN_BF16X3, P, 32 * NQ, 0, false, false, tcn_block_bf16x3_kernel<P, NQ>, "tcn_block_bf16x3_kernel"}
+#define TCN_X3_HALF_KERNEL(P, NQ, CM) \
+    {TCN_BF16X3_HALF, P, 32 * NQ, CM, false, false, tcn_block_bf16x3_half_kernel<P, NQ, CM>, "tcn_block_bf16x3_half_kernel"}
+#define TCN_F32_KERNEL(P) {TCN_F32, P, 256, 0, false, false, tcn_block_f32_kernel<P>, "tcn_block_f32_kernel"}
+const TcnBlockKernel TCN_BLOCK_KERNELS[] = {
+    //              P   head   NQ WHOLE block 0
+    TCN_BF16_KERNEL(1,  false, 8, 0, false),      // tap-major 256-time tiles: odd dilations ...
+    TCN_BF16_KERNEL(1,  true,  8, 0, false),
+    TCN_BF16_KERNEL(2,  false, 8, 0, false),      // ... and, in form 0 (bits 1-2 = 0), every two- / four-phase block
+    TCN_BF16_KERNEL(2,  true,  8, 0, false),      // a two-phase last block is tap-major in either form
+    TCN_BF16_KERNEL(4,  false, 8, 0, false),
+    TCN_BF16_KERNEL(4,  true,  8, 0, false),      // form 2 without bit 7: the head of a long segment
+    TCN_BF16_KERNEL(16, false, 8, 0, false),      // fewer than 16 steps per phase
+    TCN_BF16_KERNEL(16, true,  8, 0, false),
+    TCN_BF16_KERNEL(2,  false, 8, 2, false),      // form 2: class-major 256-time tiles
+    TCN_BF16_KERNEL(2,  false, 8, 2, true),       // bit 5: with block 0 in the staging
+    TCN_BF16_KERNEL(4,  false, 8, 2, false),
+    TCN_BF16_KERNEL(4,  true,  8, 2, false),      // bit 7: the class-major head of a long segment
+    TCN_BF16_KERNEL(4,  false, 8, 1, false),      // bit 7: one 256-time tile is the whole phase sequence (64 / 32 / 16 steps) ...
+    TCN_BF16_KERNEL(8,  false, 8, 1, false),
+    TCN_BF16_KERNEL(16, false, 8, 1, false),
+    TCN_BF16_KERNEL(16, true,  8, 1, false),      // ... with the head at sixteen phases only (registers)
+    TCN_BF16_KERNEL(4,  false, 4, 0, false),      // 128-time tiles: four phases at 17 ... 32 steps per phase (WHOLE at exactly 32) ...
+    TCN_BF16_KERNEL(4,  true,  4, 0, false),
+    TCN_BF16_KERNEL(4,  false, 4, 1, false),
+    TCN_BF16_KERNEL(4,  true,  4, 1, false),
+    TCN_BF16_KERNEL(8,  false, 4, 0, false),      // ... eight phases below and above that (WHOLE at exactly 16 steps)
+    TCN_BF16_KERNEL(8,  true,  4, 0, false),
+    TCN_BF16_KERNEL(8,  false, 4, 1, false),
+    TCN_BF16_KERNEL(8,  true,  4, 1, false),
+    //            P  NQ
+    TCN_X3_KERNEL(1, 8),
+    TCN_X3_KERNEL(2, 8),
+    TCN_X3_KERNEL(4, 8),
+    TCN_X3_KERNEL(1, 4),                          // bit 0: 128-time tiles
+    TCN_X3_KERNEL(2, 4),
+    //                 P  NQ CM
+    TCN_X3_HALF_KERNEL(8, 4, false),
+    TCN_X3_HALF_KERNEL(8, 4, true),               // bit 6
+    TCN_F32_KERNEL(1),
+    TCN_F32_KERNEL(2),
+    TCN_F32_KERNEL(4),
+    TCN_F32_KERNEL(8),
+    TCN_F32_KERNEL(16),
+};
+#undef TCN_BF16_KERNEL
+#undef TCN_X3_KERNEL
+#undef TCN_X3_HALF_KERNEL
+#undef TCN_F32_KERNEL
+
+int tcn_launch_block(const TcnBlockPlan &p, const TcnBlockArgs &a, void *stream) {
+    for (const TcnBlockKernel &k : TCN_BLOCK_KERNELS)
+        if (k.family == p.family && k.P == p.P && k.tile == p.tile && k.form == p.form && k.block0 == p.block0 &&
+            (k.head == p.head || p.family != TCN_BF16)) {
+            MST_LAUNCH(k.kernel, dim3((unsigned)p.grid), dim3(256), stream, a);
+            MST_CHECK_LAUNCH(k.name);
+            return MST_OK;
+        }
+    return fail(MST_ERR_STATE, "mst_tcn_forward: no block kernel of this tile form (with the fused head the whole-sequence 256-time tile exists at "
+                               "sixteen phases only)");
 }
 
 int tcn_run_generic(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, int n_run, void *ws, void *stream) {
@@ -447,25 +441,27 @@ int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, i
     const size_t need = mst_tcn_workspace_bytes(t, B, L, precision);
     if (!ws || ws_bytes < need) return fail(MST_ERR_WORKSPACE, "mst_tcn_forward: workspace too small");
     if (t->generic) return tcn_run_generic(t, x, y, act_out, B, L, n_run, ws, stream);
-    const size_t es = tcn_elem(precision);
-    const size_t buf_bytes = align_up((size_t)B * L * 128 * es, 256);
+    const int nblocks = t->d.nblocks;
+    TcnBlockPlan plan[MST_MAX_BLOCKS] = {};
+    for (int n = 1; n < n_run; ++n) {
+        // (block 0 moves into block 1's launch only for a net that goes on behind block 1; its own probe, n_run == 1, always runs the separate kernel)
+        plan[n] = tcn_plan_block(t->tuning, precision, t->d.dilations[n], L, B, !act_out && n == nblocks - 1,
+                                 n == 1 && nblocks > 2 && t->d.dilations[0] == 1);
+        if (plan[n].grid > 0x7fffffffL) return fail(MST_ERR_ARG, "mst_tcn_forward: grid too large");
+    }
+    const size_t buf_bytes = align_up((size_t)B * L * 128 * tcn_elem(precision), 256);
     unsigned char *buf[2] = {(unsigned char *)ws, (unsigned char *)ws + buf_bytes};
     const int Lp = L;
     hipEvent_t *ev = nullptr;
     if (!act_out && t->ev_used < t->ev_max) {
-        ev = t->ev.data() + (size_t)t->ev_used * (t->d.nblocks + 2);
+        ev = t->ev.data() + (size_t)t->ev_used * (nblocks + 2);
         t->ev_used++;
         MST_HIP_TRY(hipEventRecord(ev[0], (hipStream_t)stream));
     }
 
-    // block 0 inside block 1's launch (bf16, tuning bit 5): block 1 must be the d = 2 block on two-phase class-major tiles (form 2) and not
-    // the last block; the probes of block 0 itself (n_run == 1) always run the separate kernel
-    const bool fuse0 = precision == MST_PREC_BF16 && t->bf16_fuse0() && t->blk[0].w_bf16 && n_run >= 2 &&
-                       t->d.nblocks > 2 && t->d.dilations[0] == 1 && t->d.dilations[1] == 2 && choose_phases(2, L, precision) == 2;
+    const bool fuse0 = plan[1].block0;
     t->last_fused0 = fuse0 ? 1 : 0;
-    if (fuse0) {
-        if (ev) MST_HIP_TRY(hipEventRecord(ev[1], (hipStream_t)stream));
-    } else {
+    if (!fuse0) {
         TcnBlock0Args a;
         a.x = x;
         a.y = buf[0];
@@ -477,46 +473,17 @@ int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, i
         a.B = B;
         a.L = L;
         a.Lp = Lp;
-        const int grid = B * ((L + 511) / 512);      // 8 tiles of 64 steps per workgroup
         a.wpk16 = t->blk[0].w_bf16;
-        if (precision == MST_PREC_BF16 && a.wpk16)
+        if (precision == MST_PREC_BF16)
             MST_LAUNCH(tcn_block0_mfma_kernel, dim3(B * ((L + 255) / 256)), dim3(256), stream, a);
-        else if (precision == MST_PREC_BF16)
-            MST_LAUNCH((tcn_block0_kernel<__bf16>), dim3(grid), dim3(256), stream, a);
         else
-            MST_LAUNCH((tcn_block0_kernel<float>), dim3(grid), dim3(256), stream, a);
+            MST_LAUNCH((tcn_block0_kernel<float>), dim3(B * ((L + 511) / 512)), dim3(256), stream, a);      // 8 tiles of 64 steps per workgroup
         MST_CHECK_LAUNCH("tcn_block0_kernel");
-        if (ev) MST_HIP_TRY(hipEventRecord(ev[1], (hipStream_t)stream));
     }
+    if (ev) MST_HIP_TRY(hipEventRecord(ev[1], (hipStream_t)stream));
     int cur = 0;
-    bool fused_head = false;
     for (int n = 1; n < n_run; ++n) {
-        const int d = t->d.dilations[n];
-        int P = choose_phases(d, L, (precision == MST_PREC_BF16X3 && t->x3_small_tiles()) ? MST_PREC_BF16X3 + 100 : precision);
-        const int x3_small = (precision == MST_PREC_BF16X3 && t->x3_small_tiles() && P <= 2) ? 1 : 0;
-        // bf16, 17 ... 32 steps per phase (d = 4096 at L = 131072): 128-time tiles of FOUR phases x 32 steps (184 rows staged per 128
-        // outputs, three workgroups per CU) instead of eight phases x 16 steps (240 rows, two workgroups per CU)
-        int bf16_tile = TILE_DEFAULT;
-        if (precision == MST_PREC_BF16 && P == 8) {
-            const long ns = ((long)L + d - 1) / d;
-            if (ns > 16 && ns <= 32) {
-                P = 4;
-                bf16_tile = TILE_128_FOUR_PHASES;
-            }
-        }
-        // bf16 (tuning bit 7), a block whose phase sequences are EXACTLY one 256-time tile - sixteen phases x 16 steps (d = 8192 at L = 131072, the last
-        // block), eight x 32 (d = 4096), four x 64 (d = 2048): the unrolled class-major loop without the all-padding (column tile, tap) pairs, an LDS image
-        // without the halo steps no live row window reaches (256 / 272 / 280 rows), two workgroups per CU
-        if (precision == MST_PREC_BF16 && t->bf16_whole()) {
-            const long ns = ((long)L + d - 1) / d;
-            const int Pw = ns == 16 ? 16 : (ns == 32 ? 8 : (ns == 64 ? 4 : 0));
-            // (with the fused output head - the last block - only the sixteen-phase form fits 256 registers: 248; the other two would spill)
-            const bool head = !act_out && n == t->d.nblocks - 1;
-            if (Pw && d % Pw == 0 && (long)L == ns * d && (!head || Pw == 16)) {
-                P = Pw;
-                bf16_tile = TILE_WHOLE_256;
-            }
-        }
+        const TcnBlockPlan &p = plan[n];
         TcnBlockArgs a;
         a.x = buf[cur];
         a.y = buf[cur ^ 1];
@@ -528,39 +495,24 @@ int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, i
         a.B = B;
         a.L = L;
         a.Lp = Lp;
-        a.d = d;
-        a.tiles_phase = d / P;
-        const long nsteps = ((long)L + d - 1) / d;
-        a.tiles_step = (int)((nsteps + 256 / P - 1) / (256 / P));
-        const long grid = (long)B * a.tiles_phase * a.tiles_step;
-        // bf16 / bf16x3 modes: the last block applies the output head in its epilogue (no separate output kernel; the split mode's
-        // kernels exist for up to 8 phases - every dilation of a 2^19-sample segment - otherwise the separate head runs)
-        const bool fuse_out = (precision == MST_PREC_BF16 || (precision == MST_PREC_BF16X3 && P <= 8 && t->d.noutputs <= 2)) && !act_out &&
-                              n == t->d.nblocks - 1;
-        fused_head = fused_head || fuse_out;
+        a.d = t->d.dilations[n];
+        a.tiles_phase = p.tiles_phase;
+        a.tiles_step = p.tiles_step;
         a.out_w = t->out_w;
         a.out_b = t->out_b;
-        a.y_out = fuse_out ? y : nullptr;
+        a.y_out = p.head ? y : nullptr;
         a.nout = t->d.noutputs;
-        a.xcd_tiles = 0;
+        a.xcd_tiles = p.xcd_tiles;
         a.zeros = t->zero_row;
-        if (fuse0 && n == 1) {
+        if (p.block0) {
             a.x0 = x;
             a.w0pk = t->blk[0].w_bf16;
             a.shift0 = t->blk[0].shift;
             a.film0 = t->film;
             a.res0 = t->blk[0].res;
         }
-        if (grid > 0x7fffffffL) return fail(MST_ERR_ARG, "mst_tcn_forward: grid too large");
         int rc;
-        switch (P) {
-            case 1: rc = launch_block<1>(*t, precision, a, (int)grid, stream, x3_small, bf16_tile); break;
-            case 2: rc = launch_block<2>(*t, precision, a, (int)grid, stream, x3_small, bf16_tile); break;
-            case 4: rc = launch_block<4>(*t, precision, a, (int)grid, stream, x3_small, bf16_tile); break;
-            case 8: rc = launch_block<8>(*t, precision, a, (int)grid, stream, x3_small, bf16_tile); break;
-            default: rc = launch_block<16>(*t, precision, a, (int)grid, stream, 0, bf16_tile); break;
-        }
-        if (rc) return rc;
+        if ((rc = tcn_launch_block(p, a, stream))) return rc;
         if (ev) MST_HIP_TRY(hipEventRecord(ev[n + 1], (hipStream_t)stream));
         cur ^= 1;
     }
@@ -574,28 +526,24 @@ int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, i
         MST_CHECK_LAUNCH("tcn_unpack_kernel");
         return MST_OK;
     }
-    if (fused_head && n_run == t->d.nblocks && t->d.nblocks > 1) {
-        if (ev) {      // the output head ran inside the last block kernel
-            MST_HIP_TRY(hipEventRecord(ev[t->d.nblocks + 1], (hipStream_t)stream));
-        }
-        return MST_OK;
+    if (!plan[nblocks - 1].head) {      // (a fused head: the output conv ran inside the last block kernel)
+        TcnOutArgs o;
+        o.x = buf[cur];
+        o.y = y;
+        o.w = t->out_w;
+        o.bias = t->out_b;
+        o.nout = t->d.noutputs;
+        o.B = B;
+        o.L = L;
+        o.Lp = Lp;
+        const int grid = B * ((L + 63) / 64);
+        if (precision == MST_PREC_BF16)
+            MST_LAUNCH((tcn_output_kernel<__bf16>), dim3(grid), dim3(256), stream, o);
+        else
+            MST_LAUNCH((tcn_output_kernel<float>), dim3(grid), dim3(256), stream, o);
+        MST_CHECK_LAUNCH("tcn_output_kernel");
     }
-    TcnOutArgs o;
-    o.x = buf[cur];
-    o.y = y;
-    o.w = t->out_w;
-    o.bias = t->out_b;
-    o.nout = t->d.noutputs;
-    o.B = B;
-    o.L = L;
-    o.Lp = Lp;
-    const int grid = B * ((L + 63) / 64);
-    if (precision == MST_PREC_BF16)
-        MST_LAUNCH((tcn_output_kernel<__bf16>), dim3(grid), dim3(256), stream, o);
-    else
-        MST_LAUNCH((tcn_output_kernel<float>), dim3(grid), dim3(256), stream, o);
-    MST_CHECK_LAUNCH("tcn_output_kernel");
-    if (ev) MST_HIP_TRY(hipEventRecord(ev[t->d.nblocks + 1], (hipStream_t)stream));
+    if (ev) MST_HIP_TRY(hipEventRecord(ev[nblocks + 1], (hipStream_t)stream));
     return MST_OK;
 }
 

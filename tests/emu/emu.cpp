@@ -4,8 +4,12 @@
 // yields to the scheduler.  Workgroups are spread over OS threads (std::thread) for speed.
 #include "mst_rt.h"
 
+#include <dlfcn.h>
+
+#include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -202,4 +206,35 @@ void launch(dim3 grid, dim3 block, const std::function<void()> &body) {
     for (auto &t : th) t.join();
 }
 
+// ---- dry-run launch trace: one line "symbol gx gy gz bx" per launch.  The symbol is dladdr's name of the kernel's function pointer (the
+// instantiations are exported from libmst_emu.so), kept mangled: this toolchain's demangler stops at __bf16 template arguments.
+static bool tracing = false;
+static std::string trace;
+
+bool trace_launch(const void *kern, dim3 grid, dim3 block) {
+    if (!tracing) return false;
+    Dl_info info;
+    const char *name = (dladdr(kern, &info) && info.dli_sname && info.dli_saddr == kern) ? info.dli_sname : "?";
+    char line[512];
+    snprintf(line, sizeof(line), "%s %u %u %u %u\n", name, grid.x, grid.y, grid.z, block.x);
+    trace += line;
+    return true;
+}
+
 }  // namespace emu
+
+extern "C" void emu_trace_begin() {
+    emu::trace.clear();
+    emu::tracing = true;
+}
+
+// ends the trace and copies it (NUL-terminated, cut at cap - 1 bytes) to out; returns the length of the whole trace
+extern "C" long emu_trace_end(char *out, long cap) {
+    emu::tracing = false;
+    if (out && cap > 0) {
+        const size_t n = std::min(emu::trace.size(), (size_t)cap - 1);
+        memcpy(out, emu::trace.data(), n);
+        out[n] = 0;
+    }
+    return (long)emu::trace.size();
+}
