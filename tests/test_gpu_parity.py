@@ -7,6 +7,10 @@ Tolerances (stated per mode):
   bf16 mode  : max-abs <= 1e-2 on the waveform (bf16 operands through 14 stacked K=1920 contractions; measured 4e-3 .. 8.4e-3)
   bf16x3 mode: max-abs <= 1e-4 on the waveform like fp32 (split-bf16 operands, measured ~5e-6)
   FX         : <= 2e-6 * max|ref| (float64 internals, float32 results; energy sums accumulate in f64 here)
+  per block  : tests/test_tcn_block_exact.py, not here - each TCN block kernel alone, teacher-forced with the kernels' own activation in front of it,
+               against float64 of the same operands, EVERY element within (1 + u_out) E + u_out |y| (u_out = 2^-8 bf16, 2^-24 otherwise; E: fp32
+               accumulation 4 sqrt(K + 8) 2^-24 * sum|a W'|, the split's residual, the fp32 FiLM table and epilogue) - median bound / |y| 4.3e-3 in
+               bf16, 4e-4 (fp32) and 2e-3 (bf16x3), of the ELEMENT, where the criteria above are shares of the tensor's maximum
 """
 import os
 

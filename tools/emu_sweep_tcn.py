@@ -4,7 +4,10 @@ forms, bf16 / split-bf16 / fp32 - the module API through tests/emu against the o
 (round 4): the fixed emulator tests cover the tile kinds, this covers the shapes in between (first / last tiles full of zero rows, lengths
 around the phase-count thresholds, one-step tiles).
 
-    python tools/emu_sweep_tcn.py [--cases 40] [--seed 0]
+    python tools/emu_sweep_tcn.py [--cases 40] [--seed 0] [--exact]
+
+--exact: every block of every case, and the waveform, also against the operand-exact float64 reference of that block alone, element by
+element within its derived bound (tests/tcn_block_ref.py - the criterion of tests/test_tcn_block_exact.py, here on random shapes).
 """
 import argparse
 import os
@@ -28,6 +31,8 @@ def main():
     ap.add_argument("--only", default=None, help="restrict the sweep to one precision")
     ap.add_argument("--fuse0", action="store_true", help="bf16 cases only: also run with mst_tcn_set_tuning bit 5 (block 0 computed in block 1's "
                                                           "staging) and require the same bits")
+    ap.add_argument("--exact", action="store_true", help="also check every block alone against its float64 reference within the derived "
+                                                          "per-element bound (tests/tcn_block_ref.py)")
     args = ap.parse_args()
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     from emu_binding import bind_emulator
@@ -39,6 +44,7 @@ def main():
     _lib.set_default_binding(emu)
     rng = random.Random(args.seed)
     worst = {}
+    tracer = None
     t0 = time.time()
     for case in range(args.cases):
         growth = rng.choice([2, 2, 2, 3, 4])
@@ -68,6 +74,17 @@ def main():
         a = m.forward_blocks(x, cond, n_probe)
         erra = float((a - col[n_probe - 1]).abs().max()) / max(1e-9, float(col[n_probe - 1].abs().max()))
         ok = err <= TOL[prec] and erra <= TOL[prec]
+        if args.exact:
+            import tcn_block_ref as T
+            tracer = tracer if case else T.PlanTracer(emu)
+            dil = [growth ** n for n in range(nb)]
+            _, names, tail = tracer.checked_kernels(dil, _lib.TCN_TUNING_DEFAULT if args.tuning is None else args.tuning, B, L, prec)
+            try:
+                ratios = T.check_model(m, sd, dil, x, cond, prec, names, tail, log=lambda s: None, label=f"case {case}")
+                print(f"case {case:3d} exact: worst err / bound {max(r[0] for r in ratios.values()):.3f}")
+            except AssertionError as e:
+                print(e)
+                ok = False
         if args.fuse0:
             emu.check(emu.mst_tcn_set_tuning(m._handle, _lib.TCN_TUNING_DEFAULT | 32), "tuning")
             ok = ok and torch.equal(m(x, cond), y) and torch.equal(m.forward_blocks(x, cond, n_probe), a)
