@@ -413,6 +413,47 @@ int mst_fx_algorithmic_reverb(const float *x_dev, float *y_dev, int n_items, lon
                               double in_gain, double wet1, double wet2, double dry, double *scratch_dev, size_t scratch_bytes,
                               void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Multi-scale spectral distance: MultiScale_Spectral_Loss_MidSide_DDSP (modules/loss.py:99-213) over FrontEnd(mode=["mag"])
+ * (modules/front_back_end.py:9-82), forward only.  Per scale: torch.stft(center=True, reflect) magnitudes m = sqrt(re^2 + im^2 + 1e-7) of
+ * bins 1 .. n_fft / 2 (FrontEnd drops the DC bin) over T = 1 + L / hop frames, minus the last one when L % (n_fft / 4) == 0, of the mid /
+ * side (L + R, L - R: mode midside) or left / right (mode ori) signals of est and tgt.  One fused kernel per scale
+ * (csrc/mss_kernels.h): frames, spectra and magnitudes never reach HBM.
+ * ---------------------------------------------------------------------------------------------- */
+#define MST_MSS_MAX_SCALES 8
+#define MST_MSS_MIDSIDE 0
+#define MST_MSS_ORI 1
+#define MST_MSS_HANN 0
+#define MST_MSS_HAMMING 1
+typedef struct MstMss MstMss;
+typedef struct {
+    unsigned struct_size;                 /* = sizeof(MstMssDesc) of the caller's header; another value: MST_ERR_ARG */
+    int mode;                             /* MST_MSS_MIDSIDE / MST_MSS_ORI */
+    int n_scales;                         /* 1 .. MST_MSS_MAX_SCALES */
+    int n_fft[MST_MSS_MAX_SCALES];        /* n_filters: a power of two, 256 .. 4096 */
+    int hop[MST_MSS_MAX_SCALES];          /* hops_size: 1 .. n_fft */
+    int win_length[MST_MSS_MAX_SCALES];   /* windows_size: 1 .. n_fft; a shorter window is centred in the frame (torch.stft) */
+    int window;                           /* MST_MSS_HANN / MST_MSS_HAMMING, periodic, float64 cosine rounded once */
+    double eps;                           /* added to both magnitudes before log10 (the loss's eps, default 1e-7) */
+} MstMssDesc;
+/* anything outside the ranges above: MST_ERR_UNSUPPORTED, the message names the offending value */
+int mst_mss_create(const MstMssDesc *desc, MstMss **out);
+int mst_mss_destroy(MstMss *h);
+/* frames per (item, channel) of scale `scale` for signals of L samples (negative: MstStatus) */
+int mst_mss_frames(const MstMss *h, int scale, long L);
+size_t mst_mss_workspace_bytes(const MstMss *h, int B, long L);
+/* est_dev, tgt_dev fp32 [B, 2, L] -> terms_dev float64 [B][n_scales][2][2]: for item b, scale s, channel c (mid, side / left, right)
+ *   [0] sum over bins and frames of |m_est - m_tgt|,  [1] sum of (log10(m_est + eps) - log10(m_tgt + eps))^2
+ * (the loss's means are these sums over B * (n_fft / 2) * T).  float32 transforms, float64 sums added in a fixed order without atomics:
+ * an item's terms are the same bits in every run and in every batch; est == tgt gives exactly 0.  L must exceed n_fft / 2 of every scale
+ * (reflection padding), else MST_ERR_UNSUPPORTED. */
+int mst_mss_forward(MstMss *h, const float *est_dev, const float *tgt_dev, int B, long L, double *terms_dev, void *workspace,
+                    size_t workspace_bytes, void *stream);
+/* FrontEnd.forward(mode=["mag"]) of one scale: x_dev fp32 [B, C, L], C = 1 (channel="mono") or 2 ("stereo") -> mag_dev fp32
+ * [B, C, n_fft / 2, mst_mss_frames()].  The handle's mode and its other scales play no part: L must exceed n_fft / 2 of THIS scale.
+ * (Both entry points take at most 65535 items per call: MST_ERR_UNSUPPORTED beyond.) */
+int mst_mss_spectrogram(MstMss *h, int scale, const float *x_dev, int B, int C, long L, float *mag_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,24 @@ class MstEncDesc(C.Structure):
                 ("strides", C.c_int * MST_MAX_BLOCKS), ("dilations", C.c_int * MST_MAX_BLOCKS), ("valid_padding", C.c_int), ("act_slope", C.c_float)]
 
 
+MST_MSS_MAX_SCALES = 8
+MSS_MODES = {"midside": 0, "ori": 1}          # MST_MSS_MIDSIDE / MST_MSS_ORI
+MSS_WINDOWS = {"hann": 0, "hamming": 1}       # MST_MSS_HANN / MST_MSS_HAMMING
+
+
+class MstMssDesc(C.Structure):
+    """include/mst_hip.h MstMssDesc; struct_size is filled in here (the library refuses a struct of another layout)."""
+    _fields_ = [("struct_size", C.c_uint), ("mode", C.c_int), ("n_scales", C.c_int), ("n_fft", C.c_int * MST_MSS_MAX_SCALES),
+                ("hop", C.c_int * MST_MSS_MAX_SCALES), ("win_length", C.c_int * MST_MSS_MAX_SCALES), ("window", C.c_int),
+                ("eps", C.c_double)]
+
+    def __init__(self, mode=0, n_fft=(), hop=(), win_length=(), window=0, eps=1e-7):
+        super().__init__()
+        self.struct_size, self.mode, self.n_scales, self.window, self.eps = C.sizeof(MstMssDesc), mode, len(n_fft), window, eps
+        for i in range(min(len(n_fft), MST_MSS_MAX_SCALES)):
+            self.n_fft[i], self.hop[i], self.win_length[i] = n_fft[i], hop[i], win_length[i]
+
+
 _P = C.c_void_p
 _F = C.c_void_p   # float* passed as integer addresses (tensor.data_ptr())
 
@@ -114,6 +132,12 @@ SIGNATURES = {
                                             C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _P, C.c_size_t, _P]),
     "mst_fx_stereo_moments": (C.c_int, [_F, C.c_int, C.c_long, _P, _P]),
     "mst_fx_stereo_mix": (C.c_int, [_F, _F, C.c_int, C.c_long, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    "mst_mss_create": (C.c_int, [C.POINTER(MstMssDesc), C.POINTER(_P)]),
+    "mst_mss_destroy": (C.c_int, [_P]),
+    "mst_mss_frames": (C.c_int, [_P, C.c_int, C.c_long]),
+    "mst_mss_workspace_bytes": (C.c_size_t, [_P, C.c_int, C.c_long]),
+    "mst_mss_forward": (C.c_int, [_P, _F, _F, C.c_int, C.c_long, _P, _P, C.c_size_t, _P]),
+    "mst_mss_spectrogram": (C.c_int, [_P, C.c_int, _F, C.c_int, C.c_int, C.c_long, _F, _P]),
     "mst_fx_convolve": (C.c_int, [_P, _F, _F, C.c_long, _F, C.c_long, C.c_double, C.c_double, _P, C.c_size_t, _P]),
 }
 

@@ -1,8 +1,9 @@
 // libmst_hip.so, FX-processor part of the C ABI (mst_fx_*): equaliser, compressor, imager, gain, Haas / panner, FFT convolution, STFT,
-// algorithmic reverb - launches of csrc/fx_kernels.h and csrc/fft_kernels.h.  See include/mst_hip.h for the contract.
+// algorithmic reverb, multi-scale spectral distance - launches of csrc/fx_kernels.h, csrc/fft_kernels.h and csrc/mss_kernels.h.  See include/mst_hip.h for the contract.
 #include "mst_host.h"
 #include "fft_kernels.h"
 #include "fx_kernels.h"
+#include "mss_kernels.h"
 
 // =================================================================================================
 // FX processors
@@ -1048,4 +1049,152 @@ extern "C" int mst_fx_algorithmic_reverb(const float *x, float *y, int n_items, 
                wet2, dry);
     MST_CHECK_LAUNCH("fx_reverb_mix_kernel");
     return MST_OK;
+}
+
+// ---- multi-scale spectral distance (csrc/mss_kernels.h) ------------------------------------------------------------------
+struct MstMss {
+    MstMssDesc d;
+    int logm[MST_MSS_MAX_SCALES];                 // log2(n_fft / 2)
+    float *win[MST_MSS_MAX_SCALES];               // [n_fft]
+    float2 *tw[MST_MSS_MAX_SCALES];               // [n_fft / 4]      exp(-2 pi i j / (n_fft / 2))
+    float2 *twn[MST_MSS_MAX_SCALES];              // [n_fft / 4 + 1]  exp(-2 pi i k / n_fft)
+};
+
+namespace {
+int mss_frames(const MstMss *h, int s, long L) {          // FrontEnd: T = 1 + L // hop, minus one when L % round(n_fft / 4) == 0
+    long T = 1 + L / h->d.hop[s];
+    if (L % (h->d.n_fft[s] / 4) == 0) T -= 1;
+    return (int)T;
+}
+int mss_groups(const MstMss *h, int s, long L) {
+    const int G = MSS_PTS / h->d.n_fft[s];
+    return (mss_frames(h, s, L) + G - 1) / G;
+}
+// the scales first .. last of the handle must fit L and B the grid's z extent
+int mss_check_length(const MstMss *h, int first, int last, int B, long L, const char *who) {
+    if (B > 65535) return fail(MST_ERR_UNSUPPORTED, std::string(who) + ": B = " + std::to_string(B) + " (at most 65535 items per call)");
+    for (int s = first; s <= last; ++s) {
+        if (L <= h->d.n_fft[s] / 2 || L >= (1L << 30))
+            return fail(MST_ERR_UNSUPPORTED, std::string(who) + ": L = " + std::to_string(L) + " must exceed n_fft / 2 = " +
+                                                 std::to_string(h->d.n_fft[s] / 2) + " (reflection padding) and stay below 2^30");
+        if (mss_frames(h, s, L) < 1)
+            return fail(MST_ERR_UNSUPPORTED, std::string(who) + ": L = " + std::to_string(L) + " leaves no frame at n_fft = " +
+                                                 std::to_string(h->d.n_fft[s]) + ", hop = " + std::to_string(h->d.hop[s]));
+    }
+    return MST_OK;
+}
+template <int EPI>
+int mss_launch(const MstMss *h, int s, const float *est, const float *tgt, long item_stride, int B, int nchan, long L, int mix_mode,
+               double *terms, float *mag, int n_out, void *stream) {
+    const dim3 grid((unsigned)mss_groups(h, s, L), (unsigned)nchan, (unsigned)B);
+    const int T = mss_frames(h, s, L);
+    const float eps = (float)h->d.eps;
+#define MSS_CASE(LM)                                                                                                                  \
+    case LM:                                                                                                                          \
+        MST_LAUNCH((mss_frames_kernel<LM, EPI>), grid, dim3(256), stream, est, tgt, item_stride, (int)L, mix_mode,                   \
+                   (const float *)h->win[s], (const float2 *)h->tw[s], (const float2 *)h->twn[s], h->d.hop[s], T, eps, terms, mag, n_out); \
+        break;
+    switch (h->logm[s]) {
+        MSS_CASE(7) MSS_CASE(8) MSS_CASE(9) MSS_CASE(10) MSS_CASE(11)
+    }
+#undef MSS_CASE
+    MST_CHECK_LAUNCH("mss_frames_kernel");
+    return MST_OK;
+}
+}  // namespace
+
+extern "C" int mst_mss_destroy(MstMss *h) {
+    if (!h) return MST_OK;
+    for (int s = 0; s < MST_MSS_MAX_SCALES; ++s) {
+        (void)hipFree(h->win[s]);
+        (void)hipFree(h->tw[s]);
+        (void)hipFree(h->twn[s]);
+    }
+    delete h;
+    return MST_OK;
+}
+
+extern "C" int mst_mss_create(const MstMssDesc *desc, MstMss **out) {
+    if (!desc || !out) return fail(MST_ERR_ARG, "mst_mss_create: null argument");
+    if (desc->struct_size != sizeof(MstMssDesc)) return fail(MST_ERR_ARG, "mst_mss_create: MstMssDesc.struct_size does not match this library's layout");
+    if (desc->mode != MST_MSS_MIDSIDE && desc->mode != MST_MSS_ORI)
+        return fail(MST_ERR_UNSUPPORTED, "mst_mss_create: mode = " + std::to_string(desc->mode) + " (0 = midside, 1 = ori)");
+    if (desc->n_scales < 1 || desc->n_scales > MST_MSS_MAX_SCALES)
+        return fail(MST_ERR_UNSUPPORTED, "mst_mss_create: n_scales = " + std::to_string(desc->n_scales) + " (1 .. 8)");
+    if (desc->window != MST_MSS_HANN && desc->window != MST_MSS_HAMMING)
+        return fail(MST_ERR_UNSUPPORTED, "mst_mss_create: window = " + std::to_string(desc->window) + " (0 = hann, 1 = hamming)");
+    if (!(desc->eps >= 0.0) || !(desc->eps < 1.0)) return fail(MST_ERR_UNSUPPORTED, "mst_mss_create: eps = " + std::to_string(desc->eps) + " (0 <= eps < 1)");
+    for (int s = 0; s < desc->n_scales; ++s) {
+        const int n = desc->n_fft[s];
+        if (n < 256 || n > 4096 || (n & (n - 1)))
+            return fail(MST_ERR_UNSUPPORTED, "mst_mss_create: n_fft = " + std::to_string(n) + " (a power of two, 256 .. 4096)");
+        if (desc->hop[s] < 1 || desc->hop[s] > n)
+            return fail(MST_ERR_UNSUPPORTED, "mst_mss_create: hop = " + std::to_string(desc->hop[s]) + " (1 .. n_fft = " + std::to_string(n) + ")");
+        if (desc->win_length[s] < 1 || desc->win_length[s] > n)
+            return fail(MST_ERR_UNSUPPORTED, "mst_mss_create: win_length = " + std::to_string(desc->win_length[s]) + " (1 .. n_fft = " + std::to_string(n) + ")");
+    }
+    auto *h = new MstMss();
+    h->d = *desc;
+    const double pi = 3.14159265358979323846;
+    for (int s = 0; s < desc->n_scales; ++s) {
+        const int n = desc->n_fft[s], m = n / 2, wl = desc->win_length[s], left = (n - wl) / 2;
+        int lg = 0;
+        while ((1 << lg) < m) ++lg;
+        h->logm[s] = lg;
+        std::vector<float> win((size_t)n, 0.0f);          // periodic window, centred in the frame like torch.stft pads it
+        for (int i = 0; i < wl; ++i) {
+            const double cs = cos(2.0 * pi * (double)i / (double)wl);
+            win[(size_t)left + i] = (float)(desc->window == MST_MSS_HANN ? 0.5 - 0.5 * cs : 0.54 - 0.46 * cs);
+        }
+        std::vector<float2> tw((size_t)m / 2), twn((size_t)m / 2 + 1);
+        for (int j = 0; j < m / 2; ++j) tw[j] = make_float2((float)cos(-2.0 * pi * j / m), (float)sin(-2.0 * pi * j / m));
+        for (int k = 0; k <= m / 2; ++k) twn[k] = make_float2((float)cos(-2.0 * pi * k / n), (float)sin(-2.0 * pi * k / n));
+        int rc;
+        if ((rc = upload(&h->win[s], win)) || (rc = upload(&h->tw[s], tw)) || (rc = upload(&h->twn[s], twn))) {
+            mst_mss_destroy(h);
+            return rc;
+        }
+    }
+    *out = h;
+    return MST_OK;
+}
+
+extern "C" int mst_mss_frames(const MstMss *h, int scale, long L) {
+    if (!h || scale < 0 || scale >= h->d.n_scales || L < 1) return fail(MST_ERR_ARG, "mst_mss_frames: bad argument");
+    return mss_frames(h, scale, L);
+}
+
+extern "C" size_t mst_mss_workspace_bytes(const MstMss *h, int B, long L) {
+    if (!h || B < 1 || L < 1) return 0;
+    size_t total = 256;
+    for (int s = 0; s < h->d.n_scales; ++s) total += align_up((size_t)B * 2 * std::max(1, mss_groups(h, s, L)) * 2 * sizeof(double), 256);
+    return total;
+}
+
+extern "C" int mst_mss_forward(MstMss *h, const float *est, const float *tgt, int B, long L, double *terms, void *ws, size_t ws_bytes,
+                               void *stream) {
+    if (!h || !est || !tgt || !terms || B < 1 || L < 1) return fail(MST_ERR_ARG, "mst_mss_forward: bad argument");
+    int rc;
+    if ((rc = mss_check_length(h, 0, h->d.n_scales - 1, B, L, "mst_mss_forward"))) return rc;
+    if (!ws || ws_bytes < mst_mss_workspace_bytes(h, B, L)) return fail(MST_ERR_WORKSPACE, "mst_mss_forward: workspace null or too small");
+    unsigned char *p = (unsigned char *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    for (int s = 0; s < h->d.n_scales; ++s) {
+        double *partial = (double *)p;
+        const int groups = mss_groups(h, s, L);
+        if ((rc = mss_launch<MSS_EPI_TERMS>(h, s, est, tgt, 2 * L, B, 2, L, h->d.mode == MST_MSS_MIDSIDE ? 1 : 0, partial, nullptr, 0, stream)))
+            return rc;
+        MST_LAUNCH(mss_finalize_kernel, dim3((unsigned)((B * 4 + 63) / 64)), dim3(64), stream, (const double *)partial, terms, B, groups,
+                   h->d.n_scales, s);
+        MST_CHECK_LAUNCH("mss_finalize_kernel");
+        p += align_up((size_t)B * 2 * groups * 2 * sizeof(double), 256);
+    }
+    return MST_OK;
+}
+
+extern "C" int mst_mss_spectrogram(MstMss *h, int scale, const float *x, int B, int C, long L, float *mag, void *stream) {
+    if (!h || !x || !mag || B < 1 || L < 1 || scale < 0 || scale >= h->d.n_scales) return fail(MST_ERR_ARG, "mst_mss_spectrogram: bad argument");
+    if (C != 1 && C != 2) return fail(MST_ERR_UNSUPPORTED, "mst_mss_spectrogram: C = " + std::to_string(C) + " (1 or 2 channels)");
+    int rc;
+    if ((rc = mss_check_length(h, scale, scale, B, L, "mst_mss_spectrogram"))) return rc;
+    return mss_launch<MSS_EPI_MAG>(h, scale, x, C == 2 ? x + L : nullptr, (long)C * L, B, 1, L, 0, nullptr, mag, C, stream);
 }
