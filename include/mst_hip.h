@@ -454,6 +454,39 @@ int mst_mss_forward(MstMss *h, const float *est_dev, const float *tgt_dev, int B
  * (Both entry points take at most 65535 items per call: MST_ERR_UNSUPPORTED beyond.) */
 int mst_mss_spectrogram(MstMss *h, int scale, const float *x_dev, int B, int C, long L, float *mag_dev, void *stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Mixing-feature metrics (csrc/mixfeat_kernels.h): the per-frame work of the reference's panning, dynamics and low-frequency features
+ * (mixing_manipulator/utils_data_normalization.py: get_SPS :109-139, get_panning_rms :682-703, get_rms_dynamic_crest :777-811,
+ * get_low_freq_weighting :823-846).  Audio in the FX layout, fp32 [n_items][L][C].  Framing is librosa.stft(center = False): frame t
+ * covers samples t hop .. t hop + n_fft - 1, T = 1 + (L - n_fft) / hop frames; the window is sqrt(hanning(n_fft + 1)[:-1]).  scale_dev
+ * (fp32 [n_items], may be NULL = 1): every sample is x * scale[item], rounded to float32, before anything else
+ * (pyloudnorm.normalize.peak folded into the load).  float32 transforms and magnitudes, float64 per-bin arithmetic and sums in a fixed
+ * order without atomics: an item's numbers are the same bits alone, in a batch and from run to run.  At most 65535 items per call.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct MstMixfeat MstMixfeat;
+/* n_fft a power of two, 512 .. 4096, hop 1 .. n_fft; anything else MST_ERR_UNSUPPORTED */
+int mst_mixfeat_create(int n_fft, int hop, MstMixfeat **out);
+int mst_mixfeat_destroy(MstMixfeat *h);
+/* frames of a signal of L samples (0 when L < n_fft; negative: MstStatus) */
+int mst_mixfeat_frames(const MstMixfeat *h, long L);
+/* x_dev [n_items][L][2] -> out_dev float64 [n_items][T][n_bands]: the sum over the bins band_lo[j] <= k < band_hi[j] (host arrays,
+ * n_bands 1 .. 8, inside 0 .. n_fft / 2 + 1) of SPS_k^2, where from l = |X_left + 1e-20| and r = |X_right + 1e-20| (float32)
+ * phi = 2 l r / (l^2 + r^2) and SPS = (1 - phi) sign(r - l) in float64.  A frame with l == r in every bin (mono, digital silence) gives
+ * exactly 0. */
+int mst_mixfeat_panning(MstMixfeat *h, const float *x_dev, int n_items, long L, const float *scale_dev, const int *band_lo,
+                        const int *band_hi, int n_bands, double *out_dev, void *stream);
+/* get_SPS(frames=True): phi_dev, sps_dev fp32 [n_items][T][n_fft / 2 + 1] of x_dev [n_items][L][2] */
+int mst_mixfeat_sps(MstMixfeat *h, const float *x_dev, int n_items, long L, const float *scale_dev, float *phi_dev, float *sps_dev,
+                    void *stream);
+/* x_low_dev, x_dev [n_items][L][C], C = 1 or 2 -> out_dev float64 [n_items][C][T]: the sum over all n_fft / 2 + 1 bins of
+ * |X_low_k| / (|X_k| + 1e-5) */
+int mst_mixfeat_low_ratio(MstMixfeat *h, const float *x_low_dev, const float *x_dev, int n_items, long L, int C,
+                          const float *scale_low_dev, const float *scale_dev, double *out_dev, void *stream);
+/* x_dev [n_items][L][C], C = 1 or 2 -> out_dev float64 [n_items][C][T][3], T = 1 + (L - frame_length) / hop: per frame of frame_length
+ * samples sum x^2, sum 20 log10(|x| + 1e-30) and max |x| (a zero sample adds -600 dB, as in get_rms_dynamic_crest) */
+int mst_mixfeat_dynamics(const float *x_dev, int n_items, long L, int C, const float *scale_dev, int frame_length, int hop,
+                         double *out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,13 @@ SIGNATURES = {
     "mst_mss_workspace_bytes": (C.c_size_t, [_P, C.c_int, C.c_long]),
     "mst_mss_forward": (C.c_int, [_P, _F, _F, C.c_int, C.c_long, _P, _P, C.c_size_t, _P]),
     "mst_mss_spectrogram": (C.c_int, [_P, C.c_int, _F, C.c_int, C.c_int, C.c_long, _F, _P]),
+    "mst_mixfeat_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(_P)]),
+    "mst_mixfeat_destroy": (C.c_int, [_P]),
+    "mst_mixfeat_frames": (C.c_int, [_P, C.c_long]),
+    "mst_mixfeat_panning": (C.c_int, [_P, _F, C.c_int, C.c_long, _F, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, _P, _P]),
+    "mst_mixfeat_sps": (C.c_int, [_P, _F, C.c_int, C.c_long, _F, _F, _F, _P]),
+    "mst_mixfeat_low_ratio": (C.c_int, [_P, _F, _F, C.c_int, C.c_long, C.c_int, _F, _F, _P, _P]),
+    "mst_mixfeat_dynamics": (C.c_int, [_F, C.c_int, C.c_long, C.c_int, _F, C.c_int, C.c_int, _P, _P]),
     "mst_fx_convolve": (C.c_int, [_P, _F, _F, C.c_long, _F, C.c_long, C.c_double, C.c_double, _P, C.c_size_t, _P]),
 }
 

@@ -1,9 +1,11 @@
 // libmst_hip.so, FX-processor part of the C ABI (mst_fx_*): equaliser, compressor, imager, gain, Haas / panner, FFT convolution, STFT,
-// algorithmic reverb, multi-scale spectral distance - launches of csrc/fx_kernels.h, csrc/fft_kernels.h and csrc/mss_kernels.h.  See include/mst_hip.h for the contract.
+// algorithmic reverb, multi-scale spectral distance, mixing-feature metrics - launches of csrc/fx_kernels.h, csrc/fft_kernels.h, csrc/mss_kernels.h and
+// csrc/mixfeat_kernels.h.  See include/mst_hip.h for the contract.
 #include "mst_host.h"
 #include "fft_kernels.h"
 #include "fx_kernels.h"
 #include "mss_kernels.h"
+#include "mixfeat_kernels.h"
 
 // =================================================================================================
 // FX processors
@@ -1197,4 +1199,141 @@ extern "C" int mst_mss_spectrogram(MstMss *h, int scale, const float *x, int B, 
     int rc;
     if ((rc = mss_check_length(h, scale, scale, B, L, "mst_mss_spectrogram"))) return rc;
     return mss_launch<MSS_EPI_MAG>(h, scale, x, C == 2 ? x + L : nullptr, (long)C * L, B, 1, L, 0, nullptr, mag, C, stream);
+}
+
+// ---- mixing-feature metrics (csrc/mixfeat_kernels.h) -----------------------------------------------------------------------
+struct MstMixfeat {
+    int n_fft = 0, hop = 0, logm = 0;          // logm = log2(n_fft / 2)
+    float *win = nullptr;                      // [n_fft]          sqrt(hanning(n_fft + 1)[:-1])
+    float2 *tw = nullptr;                      // [n_fft / 4]      exp(-2 pi i j / (n_fft / 2))
+    float2 *twn = nullptr;                     // [n_fft / 4 + 1]  exp(-2 pi i k / n_fft)
+};
+
+namespace {
+long mixfeat_frames(const MstMixfeat *h, long L) { return L < h->n_fft ? 0 : 1 + (L - h->n_fft) / h->hop; }
+int mixfeat_check(const MstMixfeat *h, const void *x, const void *out, int n_items, long L, const char *who) {
+    if (!h || !x || !out || n_items < 1 || L < 1) return fail(MST_ERR_ARG, std::string(who) + ": bad argument");
+    if (n_items > 65535) return fail(MST_ERR_UNSUPPORTED, std::string(who) + ": n_items = " + std::to_string(n_items) + " (at most 65535 items per call)");
+    if (L < h->n_fft || L >= (1L << 30))
+        return fail(MST_ERR_UNSUPPORTED, std::string(who) + ": L = " + std::to_string(L) + " leaves no frame at n_fft = " + std::to_string(h->n_fft) +
+                                             " (or reaches 2^30)");
+    return MST_OK;
+}
+template <int EPI>
+int mixfeat_launch(const MstMixfeat *h, const float *xa, const float *xb, int n_items, int nchan, long L, int C, const float *sa, const float *sb,
+                   const MixfeatBands &bands, double *out_sum, float *phi, float *sps, void *stream) {
+    const int T = (int)mixfeat_frames(h, L), G = MSS_PTS / h->n_fft;
+    const dim3 grid((unsigned)((T + G - 1) / G), (unsigned)nchan, (unsigned)n_items);
+#define MIXFEAT_CASE(LM)                                                                                                              \
+    case LM:                                                                                                                          \
+        MST_LAUNCH((mixfeat_frames_kernel<LM, EPI>), grid, dim3(256), stream, xa, xb, L * C, C, sa, sb, (const float *)h->win,        \
+                   (const float2 *)h->tw, (const float2 *)h->twn, h->hop, T, bands, out_sum, phi, sps);                               \
+        break;
+    switch (h->logm) {
+        MIXFEAT_CASE(8) MIXFEAT_CASE(9) MIXFEAT_CASE(10) MIXFEAT_CASE(11)
+    }
+#undef MIXFEAT_CASE
+    MST_CHECK_LAUNCH("mixfeat_frames_kernel");
+    return MST_OK;
+}
+}  // namespace
+
+extern "C" int mst_mixfeat_destroy(MstMixfeat *h) {
+    if (!h) return MST_OK;
+    (void)hipFree(h->win);
+    (void)hipFree(h->tw);
+    (void)hipFree(h->twn);
+    delete h;
+    return MST_OK;
+}
+
+extern "C" int mst_mixfeat_create(int n_fft, int hop, MstMixfeat **out) {
+    if (!out) return fail(MST_ERR_ARG, "mst_mixfeat_create: null argument");
+    if (n_fft < 512 || n_fft > 4096 || (n_fft & (n_fft - 1)))
+        return fail(MST_ERR_UNSUPPORTED, "mst_mixfeat_create: n_fft = " + std::to_string(n_fft) + " (a power of two, 512 .. 4096)");
+    if (hop < 1 || hop > n_fft) return fail(MST_ERR_UNSUPPORTED, "mst_mixfeat_create: hop = " + std::to_string(hop) + " (1 .. n_fft = " + std::to_string(n_fft) + ")");
+    auto *h = new MstMixfeat();
+    h->n_fft = n_fft;
+    h->hop = hop;
+    const int n = n_fft, m = n / 2;
+    while ((1 << h->logm) < m) ++h->logm;
+    const double pi = 3.14159265358979323846;
+    std::vector<float> win((size_t)n);          // numpy: hanning(n + 1)[i] = 0.5 - 0.5 cos(2 pi i / n), float64; the root rounded once
+    for (int i = 0; i < n; ++i) win[i] = (float)sqrt(0.5 - 0.5 * cos(2.0 * pi * (double)i / (double)n));
+    std::vector<float2> tw((size_t)m / 2), twn((size_t)m / 2 + 1);
+    for (int j = 0; j < m / 2; ++j) tw[j] = make_float2((float)cos(-2.0 * pi * j / m), (float)sin(-2.0 * pi * j / m));
+    for (int k = 0; k <= m / 2; ++k) twn[k] = make_float2((float)cos(-2.0 * pi * k / n), (float)sin(-2.0 * pi * k / n));
+    int rc;
+    if ((rc = upload(&h->win, win)) || (rc = upload(&h->tw, tw)) || (rc = upload(&h->twn, twn))) {
+        mst_mixfeat_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return MST_OK;
+}
+
+extern "C" int mst_mixfeat_frames(const MstMixfeat *h, long L) {
+    if (!h || L < 1) return fail(MST_ERR_ARG, "mst_mixfeat_frames: bad argument");
+    return (int)mixfeat_frames(h, L);
+}
+
+extern "C" int mst_mixfeat_panning(MstMixfeat *h, const float *x, int n_items, long L, const float *scale, const int *band_lo, const int *band_hi,
+                                   int n_bands, double *out, void *stream) {
+    int rc;
+    if ((rc = mixfeat_check(h, x, out, n_items, L, "mst_mixfeat_panning"))) return rc;
+    if (!band_lo || !band_hi) return fail(MST_ERR_ARG, "mst_mixfeat_panning: null band edges");
+    if (n_bands < 1 || n_bands > MIXFEAT_MAX_BANDS)
+        return fail(MST_ERR_UNSUPPORTED, "mst_mixfeat_panning: n_bands = " + std::to_string(n_bands) + " (1 .. 8)");
+    MixfeatBands bands;
+    bands.n = n_bands;
+    for (int j = 0; j < MIXFEAT_MAX_BANDS; ++j) bands.lo[j] = bands.hi[j] = 0;
+    for (int j = 0; j < n_bands; ++j) {
+        if (band_lo[j] < 0 || band_hi[j] < band_lo[j] || band_hi[j] > h->n_fft / 2 + 1)
+            return fail(MST_ERR_ARG, "mst_mixfeat_panning: band " + std::to_string(j) + " = [" + std::to_string(band_lo[j]) + ", " +
+                                         std::to_string(band_hi[j]) + ") is not inside 0 .. n_fft / 2 + 1");
+        bands.lo[j] = band_lo[j];
+        bands.hi[j] = band_hi[j];
+    }
+    return mixfeat_launch<MIXFEAT_EPI_PANNING>(h, x, x + 1, n_items, 1, L, 2, scale, scale, bands, out, nullptr, nullptr, stream);
+}
+
+extern "C" int mst_mixfeat_sps(MstMixfeat *h, const float *x, int n_items, long L, const float *scale, float *phi, float *sps, void *stream) {
+    int rc;
+    if ((rc = mixfeat_check(h, x, phi, n_items, L, "mst_mixfeat_sps"))) return rc;
+    if (!sps) return fail(MST_ERR_ARG, "mst_mixfeat_sps: bad argument");
+    MixfeatBands bands;
+    bands.n = 0;
+    return mixfeat_launch<MIXFEAT_EPI_PANNING_STORE>(h, x, x + 1, n_items, 1, L, 2, scale, scale, bands, nullptr, phi, sps, stream);
+}
+
+extern "C" int mst_mixfeat_low_ratio(MstMixfeat *h, const float *x_low, const float *x, int n_items, long L, int C, const float *scale_low,
+                                     const float *scale, double *out, void *stream) {
+    int rc;
+    if ((rc = mixfeat_check(h, x, out, n_items, L, "mst_mixfeat_low_ratio"))) return rc;
+    if (!x_low) return fail(MST_ERR_ARG, "mst_mixfeat_low_ratio: bad argument");
+    if (C != 1 && C != 2) return fail(MST_ERR_UNSUPPORTED, "mst_mixfeat_low_ratio: C = " + std::to_string(C) + " (1 or 2 channels)");
+    MixfeatBands bands;
+    bands.n = 1;
+    return mixfeat_launch<MIXFEAT_EPI_LOW_RATIO>(h, x_low, x, n_items, C, L, C, scale_low, scale, bands, out, nullptr, nullptr, stream);
+}
+
+extern "C" int mst_mixfeat_dynamics(const float *x, int n_items, long L, int C, const float *scale, int frame_length, int hop, double *out,
+                                    void *stream) {
+    if (!x || !out || n_items < 1 || L < 1) return fail(MST_ERR_ARG, "mst_mixfeat_dynamics: bad argument");
+    if (C != 1 && C != 2) return fail(MST_ERR_UNSUPPORTED, "mst_mixfeat_dynamics: C = " + std::to_string(C) + " (1 or 2 channels)");
+    if (n_items > 65535) return fail(MST_ERR_UNSUPPORTED, "mst_mixfeat_dynamics: n_items = " + std::to_string(n_items) + " (at most 65535 items per call)");
+    if (frame_length < 1 || frame_length > (1 << 20))
+        return fail(MST_ERR_UNSUPPORTED, "mst_mixfeat_dynamics: frame_length = " + std::to_string(frame_length) + " (1 .. 2^20)");
+    if (hop < 1) return fail(MST_ERR_UNSUPPORTED, "mst_mixfeat_dynamics: hop = " + std::to_string(hop) + " (at least 1)");
+    if (L < frame_length || L >= (1L << 30))
+        return fail(MST_ERR_UNSUPPORTED, "mst_mixfeat_dynamics: L = " + std::to_string(L) + " leaves no frame of " + std::to_string(frame_length) +
+                                             " samples (or reaches 2^30)");
+    const long T = 1 + (L - frame_length) / hop;
+    // hop blocks combined in a fixed order when hop divides the frame length (and a frame's blocks fit half a workgroup's table), else whole frames
+    const bool blocked = frame_length % hop == 0 && frame_length / hop <= MIXFEAT_DYN_BLOCKS / 2;
+    const int R = blocked ? frame_length / hop : 1, blk = blocked ? hop : frame_length, fpw = MIXFEAT_DYN_BLOCKS - R + 1;
+    MST_LAUNCH(mixfeat_dynamics_kernel, dim3((unsigned)((T + fpw - 1) / fpw), 1, (unsigned)n_items), dim3(256), stream, x, L * C, C, scale, blk,
+               hop, R, fpw, (int)T, out);
+    MST_CHECK_LAUNCH("mixfeat_dynamics_kernel");
+    return MST_OK;
 }

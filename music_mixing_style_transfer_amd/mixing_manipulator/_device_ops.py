@@ -190,3 +190,146 @@ def onset_hfc(x, win, channel=0):
         with lib.device_ctx(x):
             lib.check(lib.mst_fx_onset_hfc(x.data_ptr(), n, L, Cn, channel, win, out.data_ptr(), lib.stream_ptr(x)), "mst_fx_onset_hfc")
     return out.cpu().numpy()
+
+
+# ---------------------------------------------------------------------------------------- mixing-feature metrics (csrc/mixfeat_kernels.h)
+def _batch(x):
+    """device [L, C] or [n, L, C] float32 -> contiguous [n, L, C]"""
+    return (x[None] if x.dim() == 2 else x).contiguous()
+
+
+def peaks(x):
+    """x device [n, L, C] -> float64 numpy [n]: max |x| of every item over all its channels (mst_fx_range_reduce)."""
+    n, L, Cn = x.shape
+    out = np.zeros(n)
+    for c in range(Cn):
+        out = np.maximum(out, range_reduce(x, list(range(n)), [0] * n, [L] * n, channel=c, mode="max"))
+    return out
+
+
+def _scale_ptr(scale, n, device):
+    """per-item load factor: None, or n float32 values -> (tensor kept alive, pointer)"""
+    if scale is None:
+        return None, None
+    t = torch.from_numpy(np.ascontiguousarray(scale, dtype=np.float32).reshape(n)).to(device)
+    return t, t.data_ptr()
+
+
+class MixFeat:
+    """The framed mixing-feature kernels at one (n_fft, hop): band sums of SPS^2, phi / SPS per bin, the low-frequency ratio."""
+    _cache = {}
+
+    @classmethod
+    def get(cls, n_fft, hop):
+        lib = _lib.lib()
+        key = (lib.path, int(n_fft), int(hop))
+        if key not in cls._cache:
+            if len(cls._cache) > 8:
+                cls._cache.clear()
+            cls._cache[key] = cls(lib, n_fft, hop)
+        return cls._cache[key]
+
+    def __init__(self, lib, n_fft, hop):
+        self.lib, self.n_fft, self.hop = lib, int(n_fft), int(hop)
+        self._handles = {}
+
+    def _handle(self, x):
+        key = str(x.device)
+        if key not in self._handles:
+            h = C.c_void_p()
+            with self.lib.device_ctx(x):
+                self.lib.check(self.lib.mst_mixfeat_create(self.n_fft, self.hop, C.byref(h)), "mst_mixfeat_create")
+            self._handles[key] = h
+        return self._handles[key]
+
+    def frames(self, L):
+        return max(0, 1 + (L - self.n_fft) // self.hop) if L >= self.n_fft else 0
+
+    def _stereo(self, x, what):
+        self.lib.require_device(x, what)
+        x = _batch(x)
+        if x.dtype != torch.float32 or x.shape[2] != 2:
+            raise ValueError(f"{what}: float32 [L, 2] or [n, L, 2] expected, got {x.dtype} {tuple(x.shape)}")
+        return x
+
+    def panning(self, x, bands, scale=None):
+        """x device [n, L, 2]; bands [(lo, hi)] in bins -> float64 numpy [n, T, n_bands]: sum of SPS^2 over each band, per frame"""
+        lib = self.lib
+        x = self._stereo(x, "mst_mixfeat_panning")
+        n, L, _ = x.shape
+        lo = (C.c_int * len(bands))(*[int(b[0]) for b in bands])
+        hi = (C.c_int * len(bands))(*[int(b[1]) for b in bands])
+        keep, sp = _scale_ptr(scale, n, x.device)
+        with lib.device_ctx(x):
+            out = torch.empty(n, self.frames(L), len(bands), dtype=torch.float64, device=x.device)
+            lib.check(lib.mst_mixfeat_panning(self._handle(x), x.data_ptr(), n, L, sp, lo, hi, len(bands), out.data_ptr(), lib.stream_ptr(x)),
+                      "mst_mixfeat_panning")
+        return out.cpu().numpy()
+
+    def sps(self, x, scale=None):
+        """x device [n, L, 2] -> (phi, SPS) device float32 [n, T, n_fft / 2 + 1]"""
+        lib = self.lib
+        x = self._stereo(x, "mst_mixfeat_sps")
+        n, L, _ = x.shape
+        keep, sp = _scale_ptr(scale, n, x.device)
+        with lib.device_ctx(x):
+            phi = torch.empty(n, self.frames(L), self.n_fft // 2 + 1, dtype=torch.float32, device=x.device)
+            sps = torch.empty_like(phi)
+            lib.check(lib.mst_mixfeat_sps(self._handle(x), x.data_ptr(), n, L, sp, phi.data_ptr(), sps.data_ptr(), lib.stream_ptr(x)),
+                      "mst_mixfeat_sps")
+        return phi, sps
+
+    def low_ratio(self, x_low, x, scale_low=None, scale=None):
+        """x_low, x device [n, L, C] -> float64 numpy [n, C, T]: sum over the bins of |X_low| / (|X| + 1e-5), per channel and frame"""
+        lib = self.lib
+        lib.require_device(x, "mst_mixfeat_low_ratio")
+        x_low, x = _batch(x_low), _batch(x)
+        if x.dtype != torch.float32 or x_low.dtype != torch.float32 or x.shape != x_low.shape:
+            raise ValueError(f"mst_mixfeat_low_ratio: two float32 tensors of one shape expected, got {tuple(x_low.shape)} and {tuple(x.shape)}")
+        n, L, Cn = x.shape
+        keep_a, sa = _scale_ptr(scale_low, n, x.device)
+        keep_b, sb = _scale_ptr(scale, n, x.device)
+        with lib.device_ctx(x):
+            out = torch.empty(n, Cn, self.frames(L), dtype=torch.float64, device=x.device)
+            lib.check(lib.mst_mixfeat_low_ratio(self._handle(x), x_low.data_ptr(), x.data_ptr(), n, L, Cn, sa, sb, out.data_ptr(),
+                                                lib.stream_ptr(x)), "mst_mixfeat_low_ratio")
+        return out.cpu().numpy()
+
+    def __del__(self):
+        try:
+            for h in self._handles.values():
+                self.lib.mst_mixfeat_destroy(h)
+        except Exception:
+            pass
+
+
+def frame_dynamics(x, frame_length, hop, scale=None):
+    """x device [n, L, C] -> float64 numpy [n, C, T, 3]: per frame sum x^2, sum 20 log10(|x| + 1e-30), max |x|"""
+    lib = _lib.lib()
+    lib.require_device(x, "mst_mixfeat_dynamics")
+    x = _batch(x)
+    if x.dtype != torch.float32:
+        raise ValueError(f"mst_mixfeat_dynamics: float32 expected, got {x.dtype}")
+    n, L, Cn = x.shape
+    T = 1 + (L - frame_length) // hop if L >= frame_length else 0
+    keep, sp = _scale_ptr(scale, n, x.device)
+    with lib.device_ctx(x):
+        out = torch.empty(n, Cn, T, 3, dtype=torch.float64, device=x.device)
+        lib.check(lib.mst_mixfeat_dynamics(x.data_ptr(), n, L, Cn, sp, int(frame_length), int(hop), out.data_ptr(), lib.stream_ptr(x)),
+                  "mst_mixfeat_dynamics")
+    return out.cpu().numpy()
+
+
+def biquad_cascade(x, sos):
+    """A cascade of second-order sections from rest over x device [n, L, C] (float64 recursion, float32 result); sos rows (b0, b1, b2, a0, a1, a2)"""
+    lib = _lib.lib()
+    x = _batch(x)
+    coef = np.ascontiguousarray(sos, dtype=np.float64)
+    n, L, Cn = x.shape
+    y = torch.empty_like(x)
+    with lib.device_ctx(x):
+        nbytes = lib.mst_fx_biquad_scratch_bytes(n, L, Cn, len(coef))
+        sc = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
+        lib.check(lib.mst_fx_biquad_cascade(x.data_ptr(), y.data_ptr(), n, L, Cn, coef.ctypes.data_as(C.POINTER(C.c_double)), len(coef),
+                                            sc.data_ptr(), nbytes, None, lib.stream_ptr(x)), "mst_fx_biquad_cascade")
+    return y

@@ -1,5 +1,8 @@
 """EQ and compressor matching of the input normaliser (reference mixing_manipulator/utils_data_normalization.py:
-get_eq_matching :65-107, get_mean_peak :284-338, compress :340-355, get_comp_matching :357-429).
+get_eq_matching :65-107, get_mean_peak :284-338, compress :340-355, get_comp_matching :357-429), and the audio-feature errors the
+reference judges a mix by (compute_loudness_features / compute_panning_features / compute_dynamic_features :483-905 with their helpers
+get_running_stats :41-63, get_SPS :109-139, get_panning_rms :682-703, get_rms_dynamic_crest :777-811, lowpassFiltering :813-820,
+get_low_freq_weighting :823-846).
 
 Same function names, arguments and return values as the reference (numpy in, numpy out); the sample-rate work runs on
 the MI355X:
@@ -11,7 +14,12 @@ the MI355X:
     below the target; here a whole row of threshold candidates runs as ONE batch of the time-parallel compressor kernels on
     the same input (mst_fx_compressor_grid), their onset-detection functions and inter-onset peaks are reduced on the device,
     and the first candidate in the reference's scan order that satisfies the condition is returned - the same result as the
-    sequential search.
+    sequential search;
+  * the feature errors: the per-frame work - the stereo panning spectrum's band sums, sum x^2 / sum dB / max |x| of every frame, the
+    low-passed spectrum over the spectrum - runs in csrc/mixfeat_kernels.h on `out` and `tar` as one batch of two items, with
+    pyloudnorm.normalize.peak folded into the kernels' loads; the zero-phase Butterworth low-pass is the float64 biquad cascade run
+    forwards and backwards; the short per-frame sequences come back to the host, where the running means over 40 frames, the deletion
+    of zero-rms target frames and the errors (sklearn's mean_absolute_percentage_error / mean_squared_error, restated) are float64 numpy.
 """
 import numpy as np
 import scipy.signal
@@ -194,3 +202,180 @@ def get_comp_matching(audio, ref_peak, ref_std, ratio, attack, release, sr=44100
                     return out(y[i])
             last = y[len(th_chunk) - 1]
     return out(last)                                # no setting qualified: the reference returns the last one it tried
+
+
+# ------------------------------------------------------------------------------------------------ audio-feature errors
+def running_mean_std(x, N):
+    """mean and standard deviation of every window of N consecutive values of x, from cumulative sums (float64)"""
+    x = np.asarray(x, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        c1 = np.concatenate(([0.0], np.cumsum(x)))
+        c2 = np.concatenate(([0.0], np.cumsum(x * x)))
+        mean = (c1[N:] - c1[:-N]) / float(N)
+        std = np.sqrt((c2[N:] - c2[:-N]) / N - mean * mean)
+    return mean, std
+
+
+def get_running_stats(x, features, N=20):
+    """x [frames, n_features] -> (mean, std), each [len(features), frames - N + 1]"""
+    stats = [running_mean_std(x[:, i], N) for i in range(len(features))]
+    return np.asarray([m for m, _ in stats]), np.asarray([s for _, s in stats])
+
+
+def _mape(y_true, y_pred):
+    """sklearn.metrics.mean_absolute_percentage_error"""
+    t, o = np.asarray(y_true, dtype=np.float64), np.asarray(y_pred, dtype=np.float64)
+    return float(np.mean(np.abs(t - o) / np.maximum(np.abs(t), np.finfo(np.float64).eps)))
+
+
+def _mse(y_true, y_pred):
+    """sklearn.metrics.mean_squared_error"""
+    t, o = np.asarray(y_true, dtype=np.float64), np.asarray(y_pred, dtype=np.float64)
+    return float(np.mean((t - o) ** 2))
+
+
+def _peak_gain(xb, target_db=-1.0):
+    """pyloudnorm.normalize.peak's factor of every item of a device batch [n, L, C], as the float32 a float32 signal is multiplied by"""
+    with np.errstate(divide="ignore"):
+        return (np.power(10.0, target_db / 20.0) / D.peaks(xb)).astype(np.float32)
+
+
+def _pair(audio_out, audio_tar):
+    """the two signals [L, C] as one device batch [2, L, C] (item 0 = out, 1 = tar)"""
+    import torch
+    o, t = D.to_device(audio_out), D.to_device(audio_tar)
+    if o.shape != t.shape:
+        raise ValueError(f"the two signals must have one shape, got {tuple(o.shape)} and {tuple(t.shape)}")
+    return torch.stack((o, t)).contiguous()
+
+
+def _band_bins(freqs, sr, n_fft):
+    return [(int(np.floor(f[0] * n_fft / sr)), int(np.floor(f[1] * n_fft / sr))) for f in freqs]
+
+
+def get_SPS(x, n_fft=2048, hop_length=1024, smooth=False, frames=False):
+    """Stereo panning spectrum of x [L, 2]: (SPS_mean, phi_mean, SPS, phi), the last two [frames, n_fft / 2 + 1] float32 (they stay on the
+    device when x is a device tensor), the means over the frames float64 numpy (Savitzky-Golay smoothed over 501 bins when smooth)."""
+    phi, sps = D.MixFeat.get(n_fft, hop_length).sps(D.to_device(x))
+    phi, sps = phi[0], sps[0]
+    phi_mean, sps_mean = phi.double().mean(dim=0).cpu().numpy(), sps.double().mean(dim=0).cpu().numpy()
+    if smooth:
+        phi_mean = scipy.signal.savgol_filter(phi_mean, 501, 1, mode="mirror")
+        sps_mean = scipy.signal.savgol_filter(sps_mean, 501, 1, mode="mirror")
+    if not _is_device(x):
+        phi, sps = phi.cpu().numpy(), sps.cpu().numpy()
+    return sps_mean, phi_mean, sps, phi
+
+
+def get_panning_rms_frame(sps_frame, freqs=[0, 22050], sr=44100, n_fft=2048):
+    (f1, f2), = _band_bins([freqs], sr, n_fft)
+    return np.sqrt((1 / (f2 - f1)) * np.sum(np.asarray(sps_frame[f1:f2], dtype=np.float64) ** 2))
+
+
+def get_panning_rms(sps, freqs=[[0, 22050]], sr=44100, n_fft=2048):
+    """sps [frames, bins] (numpy or device) -> [frames, len(freqs)]: the rms of SPS over each band"""
+    sps = np.asarray(sps.cpu() if _is_device(sps) else sps, dtype=np.float64)
+    return np.stack([np.sqrt((1 / (f2 - f1)) * np.sum(sps[:, f1:f2] ** 2, axis=1)) for f1, f2 in _band_bins(freqs, sr, n_fft)], axis=1)
+
+
+def _panning_rms_batch(xb, gain, freqs, sr, n_fft, hop_length):
+    """xb device [n, L, 2] -> [n, frames, len(freqs)]: get_panning_rms(get_SPS(x * gain)) in one fused kernel (no spectrum leaves the chip)"""
+    bands = _band_bins(freqs, sr, n_fft)
+    sums = D.MixFeat.get(n_fft, hop_length).panning(xb, bands, gain)
+    return np.sqrt(sums / np.asarray([f2 - f1 for f1, f2 in bands], dtype=np.float64))
+
+
+def compute_panning_features(args_):
+    audio_out_, audio_tar_, idx, sr, fft_size, hop_length = args_[:6]
+    xb = _pair(audio_out_, audio_tar_)
+    freqs = [[0, sr // 2], [0, 250], [250, 2500], [2500, sr // 2]]
+    p_rms_out, p_rms_tar = _panning_rms_batch(xb, _peak_gain(xb), freqs, sr, fft_size, hop_length)
+    if np.min(p_rms_tar) == 0.0:                      # frames with zero rms leave the target (and the same frames the output)
+        keep = p_rms_tar[:, 0] != 0
+        p_rms_tar, p_rms_out = p_rms_tar[keep], p_rms_out[keep]
+    mean_tar, _ = get_running_stats(p_rms_tar, freqs, N=40)
+    mean_out, _ = get_running_stats(p_rms_out, freqs, N=40)
+    panning_ = {key: [_mape(mean_tar[i], mean_out[i])] for i, key in enumerate(["P_t_mean", "P_l_mean", "P_m_mean", "P_h_mean"])}
+    panning_["mape_mean"] = [np.mean([panning_[k] for k in ("P_t_mean", "P_l_mean", "P_m_mean", "P_h_mean")])]
+    return panning_
+
+
+def _dynamics_from_sums(sums, frame_length):
+    """[C, T, 3] (sum x^2, sum dB, max |x|) -> rms, dynamic spread, crest factor, each [1, T]: the means over the channels"""
+    x_rms = amp_to_db(np.sqrt(sums[..., 0] / frame_length))
+    x_d = (sums[..., 1] - frame_length * x_rms) / frame_length
+    with np.errstate(divide="ignore", invalid="ignore"):
+        x_c = amp_to_db(sums[..., 2]) / x_rms                      # the reference's crest factor: a ratio of two dB values
+    return tuple(np.expand_dims(np.mean(v, axis=0), 0) for v in (x_rms, x_d, x_c))
+
+
+def get_rms_dynamic_crest(x, frame_length, hop_length):
+    return _dynamics_from_sums(D.frame_dynamics(D.to_device(x), frame_length, hop_length)[0], frame_length)
+
+
+def _lowpass_batch(xb, f0, sr):
+    """scipy.signal.filtfilt(*butter(4, f0 / (sr / 2)), x) along L of a device batch [n, L, C]: odd extension by 15 samples, then the
+    float64 biquad cascade forwards and, on the flipped signal, backwards.  scipy starts each pass in the steady state of the pass's first
+    sample (lfilter_zi); here the pass is started from rest on a run-in of that sample repeated until the transient is below float64
+    resolution - the same state without forming x - x0 in float32."""
+    import torch
+    sos = scipy.signal.butter(4, f0 / (sr / 2), "lowpass", output="sos")
+    edge = 15                                                   # 3 * max(len(a), len(b))
+    n, L, Cn = xb.shape
+    if L <= edge:
+        raise ValueError(f"The length of the input vector x must be greater than padlen, which is {edge}.")
+    radius = max(np.abs(np.roots(sec[3:])).max() for sec in sos)
+    run = int(np.ceil(np.log(1e-20) / np.log(radius)))
+
+    def one_pass(sig):
+        lead = sig[:, :1].expand(-1, run, -1)
+        return D.biquad_cascade(torch.cat((lead, sig), 1).contiguous(), sos)[:, run:]
+
+    left = 2 * xb[:, :1] - torch.flip(xb[:, 1:edge + 1], dims=(1,))
+    right = 2 * xb[:, L - 1:L] - torch.flip(xb[:, L - edge - 1:L - 1], dims=(1,))
+    y = one_pass(torch.cat((left, xb, right), 1))
+    y = torch.flip(one_pass(torch.flip(y, dims=(1,))), dims=(1,))
+    return y[:, edge:edge + L].contiguous()
+
+
+def lowpassFiltering(x, f0, sr):
+    y = _lowpass_batch(D.to_device(x)[None], f0, sr)[0]
+    return y if _is_device(x) else y.cpu().numpy()
+
+
+def get_low_freq_weighting(x, sr, n_fft, hop_length, f0=1000):
+    """[1, frames]: per frame the sum over the bins of |STFT(lowpass(x))| / (|STFT(x)| + 1e-5), averaged over the channels"""
+    xb = D.to_device(x)[None]
+    ratio = D.MixFeat.get(n_fft, hop_length).low_ratio(_lowpass_batch(xb, f0, sr), xb)[0]
+    return np.expand_dims(np.mean(ratio, axis=0), axis=0)
+
+
+def compute_dynamic_features(args_):
+    import torch
+    audio_out_, audio_tar_, idx, sr, fft_size, hop_length = args_[:6]
+    xb = _pair(audio_out_, audio_tar_)
+    gain = _peak_gain(xb)
+    sums = D.frame_dynamics(xb, fft_size, hop_length, gain)                      # [2, C, T, 3]
+    xn = xb * torch.from_numpy(gain).to(xb.device)[:, None, None]                # the low-pass filters the normalised signal
+    ratio = D.MixFeat.get(fft_size, hop_length).low_ratio(_lowpass_batch(xn, 1000, sr), xn).mean(axis=1)          # [2, T]
+    N = 40
+    (rms_out, dyn_out, crest_out), (rms_tar, dyn_tar, crest_tar) = (_dynamics_from_sums(sums[i], fft_size) for i in range(2))
+    stat = lambda v: get_running_stats(v.T, [0], N=N)[0]
+    dynamic_ = {"rms_mean": [_mape(stat(1.0 - rms_tar), stat(1.0 - rms_out))],
+                "dyn_mean": [_mape(stat(1.0 - dyn_tar), stat(1.0 - dyn_out))],
+                "crest_mean": [_mape(stat(crest_tar), stat(crest_out))]}
+    low_tar, low_out = stat(ratio[1][None]), stat(ratio[0][None])
+    dynamic_["l_ratio_mean_mape"] = [_mape(low_tar, low_out)]
+    dynamic_["l_ratio_mean_l2"] = [_mse(low_tar, low_out)]
+    dynamic_["mape_mean"] = [np.mean([dynamic_["rms_mean"], dynamic_["dyn_mean"], dynamic_["crest_mean"]])]
+    return dynamic_
+
+
+def compute_loudness_features(args_):
+    audio_out_, audio_tar_, idx, sr = args_[:4]
+    o, t = D.to_device(audio_out_), D.to_device(audio_tar_)
+    with np.errstate(divide="ignore"):
+        peak_out_db, peak_tar_db = (20.0 * np.log10(D.peaks(v[None])[0]) for v in (o, t))
+    meter = fx_utils.Meter(sr)
+    loudness_tar, loudness_out = meter.integrated_loudness(t), meter.integrated_loudness(o)
+    return {"d_lufs": [_mape([loudness_tar], [loudness_out])], "d_peak": [_mape([peak_tar_db], [peak_out_db])]}
