@@ -482,13 +482,10 @@ int enc_launch_direct(const MstEncConv &c, const float *x, void *y, bool out_nlc
             default: MST_LAUNCH((enc_direct_kernel<true, 32>), grid, dim3(256), stream, a); break;
         }
     } else {
-        switch (cm) {
-            case 2: MST_LAUNCH((enc_direct_kernel<false, 2>), grid, dim3(256), stream, a); break;
-            case 4: MST_LAUNCH((enc_direct_kernel<false, 4>), grid, dim3(256), stream, a); break;
-            case 8: MST_LAUNCH((enc_direct_kernel<false, 8>), grid, dim3(256), stream, a); break;
-            case 16: MST_LAUNCH((enc_direct_kernel<false, 16>), grid, dim3(256), stream, a); break;
-            default: MST_LAUNCH((enc_direct_kernel<false, 32>), grid, dim3(256), stream, a); break;
-        }
+        // fp32 NCL output: only the first conv of block 0 (Cout = Cin <= 4, enc_nlc_eligible) - wider instantiations had no caller
+        if (c.cout > 4) return fail(MST_ERR_UNSUPPORTED, "enc_direct_kernel: fp32 output takes at most 4 channels");
+        if (cm == 2) MST_LAUNCH((enc_direct_kernel<false, 2>), grid, dim3(256), stream, a);
+        else MST_LAUNCH((enc_direct_kernel<false, 4>), grid, dim3(256), stream, a);
     }
     MST_CHECK_LAUNCH("enc_direct_kernel");
     return MST_OK;
