@@ -50,7 +50,7 @@ typedef enum {
 
 #define MST_MAX_BLOCKS 32
 
-int mst_version(void);
+int mst_version(void);          /* 101: the mst_resample_* entry points */
 const char *mst_last_error(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -486,6 +486,35 @@ int mst_mixfeat_low_ratio(MstMixfeat *h, const float *x_low_dev, const float *x_
  * samples sum x^2, sum 20 log10(|x| + 1e-30) and max |x| (a zero sample adds -600 dB, as in get_rms_dynamic_crest) */
 int mst_mixfeat_dynamics(const float *x_dev, int n_items, long L, int C, const float *scale_dev, int frame_length, int hop,
                          double *out_dev, void *stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Sample-rate conversion (csrc/resample_kernels.h): a rational polyphase FIR resampler over the FX layout, fp32 [n_items][L][C], C = 1 or
+ * 2.  No reference counterpart: the reference's loaders raise for every rate but 44.1 kHz.  Since mst_version() 101.
+ *   ratio   up / down = rate_out / rate_in reduced by their gcd; up <= 441 and down <= 640 (8, 11.025, 16, 22.05, 24, 32, 48, 88.2, 96,
+ *           192 kHz -> 44.1 kHz, 44.1 -> 176.4 kHz), and a tile of 256 outputs may span at most 2304 input frames (down / up up to about
+ *           6): anything else MST_ERR_UNSUPPORTED, the message names the ratio.  Equal rates: MST_ERR_ARG (skip the call).
+ *   filter  half = 64 max(up, down), fc = 0.945 / max(up, down); h = up * scipy.signal.firwin(2 half + 1, fc, window = ('kaiser', 12.0)),
+ *           designed in float64 on the host and rounded once to float32.
+ *   sum     y[m] = sum_j h[m down - j up + half] x[j], x zero outside the signal: scipy.signal.resample_poly(padtype = 'constant'), output
+ *           0 on input 0, no delay.  Every product is formed in float64 (exact), added in float64 in an order that depends on m alone, and
+ *           the sum is rounded once to float32; no atomics: an item's bits are the same alone, in a batch, in chunks and in every run.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct MstResampler MstResampler;
+int mst_resample_create(int rate_in, int rate_out, MstResampler **out);
+int mst_resample_destroy(MstResampler *r);
+/* any of the four pointers may be null; taps_per_phase = 2 half_len / up + 1 products per output */
+int mst_resample_info(const MstResampler *r, int *up, int *down, int *half_len, int *taps_per_phase);
+/* ceil(n_in * up / down): the outputs of a signal of n_in frames (negative: MstStatus) */
+long mst_resample_length(const MstResampler *r, long n_in);
+/* the 2 half_len + 1 float32 prototype taps h into taps_host; n must be that count */
+int mst_resample_taps(const MstResampler *r, float *taps_host, int n);
+/* x_dev [n_items][n_in][C] holds inputs in_start .. in_start + n_in - 1 of each item's signal, the call writes outputs out_start ..
+ * out_start + n_out - 1 into y_dev [n_items][n_out][C]; inputs outside the buffer are zero.  in_start = out_start = 0 and
+ * n_out = mst_resample_length(n_in): the whole signal.  Output m reads inputs (m down - half) / up .. (m down + half) / up: a chunk whose
+ * buffer covers that range of its outputs gives the bits of the whole-signal call.  All positions are 64-bit (below 2^48); n_in and n_out
+ * below 2^30 per call, at most 65535 items; y_dev of a stereo call 8-byte aligned. */
+int mst_resample_forward(MstResampler *r, const float *x_dev, long n_in, long in_start, float *y_dev, long n_out, long out_start,
+                         int n_items, int C, void *stream);
 
 #ifdef __cplusplus
 }

@@ -145,6 +145,12 @@ SIGNATURES = {
     "mst_mixfeat_sps": (C.c_int, [_P, _F, C.c_int, C.c_long, _F, _F, _F, _P]),
     "mst_mixfeat_low_ratio": (C.c_int, [_P, _F, _F, C.c_int, C.c_long, C.c_int, _F, _F, _P, _P]),
     "mst_mixfeat_dynamics": (C.c_int, [_F, C.c_int, C.c_long, C.c_int, _F, C.c_int, C.c_int, _P, _P]),
+    "mst_resample_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(_P)]),
+    "mst_resample_destroy": (C.c_int, [_P]),
+    "mst_resample_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mst_resample_length": (C.c_long, [_P, C.c_long]),
+    "mst_resample_taps": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int]),
+    "mst_resample_forward": (C.c_int, [_P, _F, C.c_long, C.c_long, _F, C.c_long, C.c_long, C.c_int, C.c_int, _P]),
     "mst_fx_convolve": (C.c_int, [_P, _F, _F, C.c_long, _F, C.c_long, C.c_double, C.c_double, _P, C.c_size_t, _P]),
 }
 

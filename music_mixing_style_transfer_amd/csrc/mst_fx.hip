@@ -6,6 +6,7 @@
 #include "fx_kernels.h"
 #include "mss_kernels.h"
 #include "mixfeat_kernels.h"
+#include "resample_kernels.h"
 
 // =================================================================================================
 // FX processors
@@ -1335,5 +1336,120 @@ extern "C" int mst_mixfeat_dynamics(const float *x, int n_items, long L, int C, 
     MST_LAUNCH(mixfeat_dynamics_kernel, dim3((unsigned)((T + fpw - 1) / fpw), 1, (unsigned)n_items), dim3(256), stream, x, L * C, C, scale, blk,
                hop, R, fpw, (int)T, out);
     MST_CHECK_LAUNCH("mixfeat_dynamics_kernel");
+    return MST_OK;
+}
+
+// ---- polyphase resampler (csrc/resample_kernels.h) ---------------------------------------------------------------------------
+struct MstResampler {
+    int rate_in = 0, rate_out = 0, up = 0, down = 0, half = 0, T = 0;
+    std::vector<float> h;                      // the 2 half + 1 prototype taps, float32
+    float *taps = nullptr;                     // [T * up]: h, zero-padded
+};
+
+namespace {
+const long RESAMPLE_MAX_POS = 1L << 48;        // positions below it: m down + half stays far inside 63 bits
+// I0(x), the power series sum ((x / 2)^k / k!)^2: every term positive, relative error of a few float64 steps at x <= 12
+double resample_i0(double x) {
+    const double q = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 200 && term > 1e-18 * sum; ++k) {
+        term *= q / ((double)k * (double)k);
+        sum += term;
+    }
+    return sum;
+}
+int resample_gcd(int a, int b) {
+    while (b) { const int t = a % b; a = b; b = t; }
+    return a;
+}
+}  // namespace
+
+extern "C" int mst_resample_destroy(MstResampler *r) {
+    if (!r) return MST_OK;
+    (void)hipFree(r->taps);
+    delete r;
+    return MST_OK;
+}
+
+extern "C" int mst_resample_create(int rate_in, int rate_out, MstResampler **out) {
+    if (!out) return fail(MST_ERR_ARG, "mst_resample_create: null argument");
+    if (rate_in < 1 || rate_out < 1)
+        return fail(MST_ERR_ARG, "mst_resample_create: rates " + std::to_string(rate_in) + " -> " + std::to_string(rate_out) + " (positive rates)");
+    if (rate_in == rate_out) return fail(MST_ERR_ARG, "mst_resample_create: equal rates (" + std::to_string(rate_in) + "): nothing to resample");
+    const int g = resample_gcd(rate_in, rate_out), up = rate_out / g, down = rate_in / g;
+    const std::string ratio = std::to_string(rate_in) + " -> " + std::to_string(rate_out) + " Hz = " + std::to_string(up) + " / " + std::to_string(down);
+    if (up > 441 || down > 640) return fail(MST_ERR_UNSUPPORTED, "mst_resample_create: " + ratio + " (up <= 441 and down <= 640)");
+    const int mx = std::max(up, down), half = 64 * mx, n = 2 * half + 1, T = 2 * half / up + 1;
+    const long span = ((long)up - 1 + (long)(RESAMPLE_TILE - 1) * down) / up + T;          // input frames under one tile of outputs, at most
+    if (span * 2 > RESAMPLE_LDS_FLOATS)
+        return fail(MST_ERR_UNSUPPORTED, "mst_resample_create: " + ratio + ": a tile of " + std::to_string(RESAMPLE_TILE) + " outputs spans " +
+                                             std::to_string(span) + " input frames (at most " + std::to_string(RESAMPLE_LDS_FLOATS / 2) + ")");
+    auto *r = new MstResampler();
+    r->rate_in = rate_in; r->rate_out = rate_out; r->up = up; r->down = down; r->half = half; r->T = T;
+    // up * scipy.signal.firwin(n, fc, window = ('kaiser', 12)), float64: sinc low-pass at fc (in units of Nyquist), Kaiser window, unit DC gain
+    const double pi = 3.14159265358979323846, fc = 0.945 / (double)mx, beta = 12.0, i0b = resample_i0(beta);
+    std::vector<double> gv((size_t)n);
+    double sum = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const double m = (double)(i - half), a = pi * (fc * m), u = m / (double)half;          // numpy.sinc's pi * x of x = fc m
+        const double sinc = i == half ? 1.0 : sin(a) / a;
+        gv[i] = fc * sinc * resample_i0(beta * sqrt(std::max(0.0, 1.0 - u * u))) / i0b;
+        sum += gv[i];
+    }
+    r->h.resize((size_t)n);
+    for (int i = 0; i < n; ++i) r->h[i] = (float)((double)up * gv[i] / sum);
+    std::vector<float> tab((size_t)T * up, 0.0f);
+    std::copy(r->h.begin(), r->h.end(), tab.begin());
+    const int rc = upload(&r->taps, tab);
+    if (rc) {
+        mst_resample_destroy(r);
+        return rc;
+    }
+    *out = r;
+    return MST_OK;
+}
+
+extern "C" int mst_resample_info(const MstResampler *r, int *up, int *down, int *half_len, int *taps_per_phase) {
+    if (!r) return fail(MST_ERR_ARG, "mst_resample_info: null handle");
+    if (up) *up = r->up;
+    if (down) *down = r->down;
+    if (half_len) *half_len = r->half;
+    if (taps_per_phase) *taps_per_phase = r->T;
+    return MST_OK;
+}
+
+extern "C" long mst_resample_length(const MstResampler *r, long n_in) {
+    if (!r || n_in < 0 || n_in >= RESAMPLE_MAX_POS) return fail(MST_ERR_ARG, "mst_resample_length: bad argument");
+    return (n_in * r->up + r->down - 1) / r->down;
+}
+
+extern "C" int mst_resample_taps(const MstResampler *r, float *taps_host, int n) {
+    if (!r || !taps_host) return fail(MST_ERR_ARG, "mst_resample_taps: null argument");
+    if (n != 2 * r->half + 1)
+        return fail(MST_ERR_ARG, "mst_resample_taps: n = " + std::to_string(n) + " (the filter has " + std::to_string(2 * r->half + 1) + " taps)");
+    std::copy(r->h.begin(), r->h.end(), taps_host);
+    return MST_OK;
+}
+
+extern "C" int mst_resample_forward(MstResampler *r, const float *x, long n_in, long in_start, float *y, long n_out, long out_start, int n_items,
+                                    int C, void *stream) {
+    if (!r || !x || !y) return fail(MST_ERR_ARG, "mst_resample_forward: null argument");
+    if (C != 1 && C != 2) return fail(MST_ERR_ARG, "mst_resample_forward: C = " + std::to_string(C) + " (1 or 2 channels)");
+    if (n_items < 1 || n_in < 1 || n_out < 1 || in_start < 0 || out_start < 0) return fail(MST_ERR_ARG, "mst_resample_forward: bad argument");
+    if (C == 2 && ((uintptr_t)y & 7)) return fail(MST_ERR_ARG, "mst_resample_forward: y_dev of a stereo call must be 8-byte aligned");
+    if (n_items > 65535) return fail(MST_ERR_UNSUPPORTED, "mst_resample_forward: n_items = " + std::to_string(n_items) + " (at most 65535 items per call)");
+    if (n_in >= (1L << 30) || n_out >= (1L << 30))
+        return fail(MST_ERR_UNSUPPORTED, "mst_resample_forward: " + std::to_string(n_in) + " -> " + std::to_string(n_out) +
+                                             " frames in one call (below 2^30 each: cut a longer signal into chunks)");
+    if (in_start >= RESAMPLE_MAX_POS || out_start >= RESAMPLE_MAX_POS)
+        return fail(MST_ERR_UNSUPPORTED, "mst_resample_forward: in_start / out_start reach 2^48");
+    const dim3 grid((unsigned)((n_out + RESAMPLE_TILE - 1) / RESAMPLE_TILE), 1, (unsigned)n_items);
+    if (C == 2)
+        MST_LAUNCH(resample_kernel<2>, grid, dim3(RESAMPLE_TILE), stream, x, n_in, in_start, y, n_out, out_start, (const float *)r->taps, r->up,
+                   r->down, r->half, r->T);
+    else
+        MST_LAUNCH(resample_kernel<1>, grid, dim3(RESAMPLE_TILE), stream, x, n_in, in_start, y, n_out, out_start, (const float *)r->taps, r->up,
+                   r->down, r->half, r->T);
+    MST_CHECK_LAUNCH("resample_kernel");
     return MST_OK;
 }

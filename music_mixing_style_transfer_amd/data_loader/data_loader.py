@@ -40,13 +40,15 @@ class Song_Dataset_Inference:
         self.device = None
         self.workers = int(getattr(args, "workers", 0) or 0)
         self._preread = None
+        # convert (args.convert_input, off by default: the reference raises): stems at another sample rate are resampled on the device
+        # (csrc/resample_kernels.h) and 24-bit PCM is accepted
+        self.convert = bool(getattr(args, "convert_input", False))
         # dist (set by the runner when it runs on several ranks): the stems that need host / normaliser work are prepared by ONE rank each
         # (stem j by rank j % world) and broadcast - the normaliser, the expensive part of a song's preparation, is sharded by stems
         self.dist = None
 
     def _prepared_by_owner(self, idx, which, inst, j):
         """Input stem j of a multi-rank run: decoded + normalised by rank j % world, received by the others (one broadcast of [2, L])."""
-        from .loader_utils import load_wav_length
         dist = self.dist
         rank, world = dist.get_rank(), dist.get_world_size()
         owner = j % world
@@ -55,13 +57,23 @@ class Song_Dataset_Inference:
             t = self._stem(idx, which, inst, normalize=True).contiguous()
         else:
             dev = self.device if (self.device is not None and dist.get_backend() == "nccl") else "cpu"
-            t = torch.empty(2, load_wav_length(path), dtype=torch.float32, device=dev)
+            t = torch.empty(2, self._frames(path), dtype=torch.float32, device=dev)
         if dist.get_backend() != "nccl" and t.is_cuda:          # test hook (gloo with several ranks on one GPU): through the host
             h = t.cpu()
             dist.broadcast(h, src=owner)
             return h.to(t.device)
         dist.broadcast(t, src=owner)
         return t.to(self.device) if self.device is not None else t
+
+    def _frames(self, path):
+        """frames of the stem as _stem returns it: the file's, or mst_resample_length of them when the file's rate is converted"""
+        import wave
+        with wave.open(path, "r") as w:
+            rate, n = w.getframerate(), w.getnframes()
+        if self.convert and rate != self.args.sample_rate:
+            from ..mixing_manipulator._device_ops import Resampler
+            return Resampler.get(rate, self.args.sample_rate).length(n)
+        return n
 
     def __len__(self):
         return len(self.data_dir_paths)
@@ -70,7 +82,7 @@ class Song_Dataset_Inference:
         path = os.path.join(self.data_dir_paths[idx], self.stem_level_directory_name, which, inst + ".wav")
         if self.device is not None:
             try:
-                wav = load_wav_device(path, self.device, sample_rate=self.args.sample_rate, preread=self._preread)      # float32 [2, L] on the device
+                wav = load_wav_device(path, self.device, sample_rate=self.args.sample_rate, preread=self._preread, convert=self.convert)      # float32 [2, L] on the device
             except ValueError as e:
                 if "stereo files only" not in str(e):
                     raise
@@ -79,7 +91,7 @@ class Song_Dataset_Inference:
                 if normalize:
                     wav = self.normalization_chain.normalize_audio(wav.t().contiguous(), src=inst).t().contiguous()
                 return torch.clamp(wav.float(), min=-1, max=1)
-        wav = load_wav_segment(path, axis=0, sample_rate=self.args.sample_rate, preread=self._preread)
+        wav = load_wav_segment(path, axis=0, sample_rate=self.args.sample_rate, preread=self._preread, convert=self.convert)
         if normalize:           # only the input stems are normalised (:586-587)
             wav = self.normalization_chain.normalize_audio(wav.transpose(), src=inst).transpose()
         return torch.clamp(torch.from_numpy(wav).float(), min=-1, max=1)

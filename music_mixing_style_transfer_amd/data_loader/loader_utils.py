@@ -1,7 +1,8 @@
 """WAV I/O helpers of the inference data path (reference data_loader/loader_utils.py:40-70).
 
 16/32-bit PCM -> float64 in [-1, 1) exactly like the reference (int16 / 2**15, int32 / 2**31), stereo
-de-interleaved to [2, L] (axis=0) or [L, 2] (axis=1).  Same ValueErrors for a wrong sample rate / bit depth.
+de-interleaved to [2, L] (axis=0) or [L, 2] (axis=1).  Same ValueErrors for a wrong sample rate / bit depth; with convert=True
+(no counterpart in the reference) the loaders take 24-bit PCM and resample a file at another rate on the device instead.
 soundfile is not a dependency: writing uses the standard `wave` module (PCM_16); `SlicedWavWriter` lets every rank of a
 multi-GPU run write the time range it produced straight into the output file (no gather of the audio to one rank).
 """
@@ -26,10 +27,32 @@ def read_wav_raw(audio_path):
     return rate, width, nch, n, raw
 
 
-def load_wav_segment(audio_path, start_point=None, duration=None, axis=1, sample_rate=44100, preread=None):
+def _resample(x, rate_in, rate_out):
+    from ..mixing_manipulator._device_ops import resample
+    return resample(x, rate_in, rate_out)
+
+
+def pcm24_to_int32(raw):
+    """24-bit PCM bytes (three per sample, little-endian) -> int32, sign-extended"""
+    b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+    v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+    return (v ^ 0x800000) - 0x800000
+
+
+def load_wav_segment(audio_path, start_point=None, duration=None, axis=1, sample_rate=44100, preread=None, convert=False):
+    """convert=True (off by default: the reference raises): 24-bit PCM is accepted (int / 2**23 in float64), and a file at another rate is
+    decoded whole, resampled to sample_rate on the device (mixing_manipulator/_device_ops.resample: float32 in, float32 out) and returned as
+    float64 like every other file; start_point and duration then count frames at sample_rate."""
     start_point = 0 if start_point is None else start_point
     if preread is not None and audio_path in preread:          # the whole file is in memory already
         rate, width, nch, n, raw = preread[audio_path]
+    else:
+        rate = None
+    foreign = convert and (rate if rate is not None else _wav_rate(audio_path)) != sample_rate
+    if foreign:                                                # another rate: the whole file, cut after the conversion
+        if rate is None:
+            rate, width, nch, n, raw = read_wav_raw(audio_path)
+    elif rate is not None:
         duration = n if duration is None else duration
         if rate != sample_rate:
             raise ValueError(f"ValueError: input audio's sample rate should be {sample_rate}")
@@ -47,33 +70,52 @@ def load_wav_segment(audio_path, start_point=None, duration=None, axis=1, sample
         X = np.frombuffer(raw, dtype=np.int16) / float(2 ** 15)
     elif width == 4:
         X = np.frombuffer(raw, dtype=np.int32) / float(2 ** 31)
+    elif width == 3 and convert:
+        X = pcm24_to_int32(raw) / float(2 ** 23)
     else:
         raise ValueError("ValueError: input audio's bit depth should be 16 or 32-bit")
+    if foreign:
+        import torch
+        Y = _resample(torch.from_numpy(X.reshape(-1, nch).astype(np.float32)), rate, sample_rate).cpu().numpy().astype(np.float64)
+        a = min(max(0, start_point), len(Y))
+        X = Y[a:len(Y) if duration is None else a + duration].reshape(-1)
     if nch == 2:
         X = np.concatenate((np.expand_dims(X[::2], axis=axis), np.expand_dims(X[1::2], axis=axis)), axis=axis)
     return X
 
 
-def load_wav_device(audio_path, device, sample_rate=44100, preread=None):
+def _wav_rate(audio_path):
+    with wave.open(audio_path, "r") as w:
+        return w.getframerate()
+
+
+def load_wav_device(audio_path, device, sample_rate=44100, preread=None, convert=False):
     """The whole file as a float32 DEVICE tensor [2, L] (load_wav_segment(path, axis=0) followed by the dataset's `.float()`): the raw
     PCM frames are uploaded as they are (2 or 4 bytes per sample instead of a float64 array made on the host) and de-interleaved /
     scaled on the device - int / 2**15 (2**31) in float64, then rounded to float32, exactly the reference's two steps.  Stereo only
-    (what the stems are); other channel counts go through load_wav_segment.  preread: {path: read_wav_raw(path)} of files already in memory."""
+    (what the stems are); other channel counts go through load_wav_segment.  preread: {path: read_wav_raw(path)} of files already in memory.
+    convert=True (off by default: the reference raises): 24-bit PCM is accepted (three bytes little-endian, sign-extended, / 2**23 in
+    float64), and a file at another rate is resampled to sample_rate on the device (_device_ops.resample) before the final transpose."""
     import torch
     rate, width, nch, n, raw = preread[audio_path] if (preread is not None and audio_path in preread) else read_wav_raw(audio_path)
-    if rate != sample_rate:
+    if rate != sample_rate and not convert:
         raise ValueError(f"ValueError: input audio's sample rate should be {sample_rate}")
-    if width not in (2, 4):
+    if width not in ((2, 3, 4) if convert else (2, 4)):
         raise ValueError("ValueError: input audio's bit depth should be 16 or 32-bit")
     if nch != 2:
         raise ValueError("load_wav_device: stereo files only")
     import warnings
     with warnings.catch_warnings():          # the frames are only read (uploaded): no writable copy of the file's 30 MB
         warnings.simplefilter("ignore")
-        host = torch.frombuffer(raw, dtype=torch.int16 if width == 2 else torch.int32)
-    dev = host.to(device, non_blocking=False).view(-1, 2)
-    x = dev.to(torch.float64) / float(2 ** 15 if width == 2 else 2 ** 31)
-    return x.to(torch.float32).t().contiguous()
+        host = torch.frombuffer(raw, dtype={2: torch.int16, 3: torch.uint8, 4: torch.int32}[width])
+    dev = host.to(device, non_blocking=False)
+    if width == 3:
+        b = dev.view(-1, 3).to(torch.int32)
+        dev = ((b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)) ^ 0x800000) - 0x800000
+    x = (dev.view(-1, 2).to(torch.float64) / float(2 ** (8 * width - 1))).to(torch.float32)
+    if rate != sample_rate:
+        x = _resample(x, rate, sample_rate)
+    return x.t().contiguous()
 
 
 def pcm16_device(x):

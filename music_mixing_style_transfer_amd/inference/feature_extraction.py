@@ -34,6 +34,7 @@ class FXencoder_Inference:
         self.output_dir = args.target_dir if args.output_dir is None else args.output_dir
         self.target_dir = args.target_dir
         self.models = {"effects_encoder": FXencoder(args.cfg_encoder).to(self.device).eval()}
+        self.convert = bool(getattr(args, "convert_input", False))
         self.models["effects_encoder"].precision = getattr(args, "precision", "fp32")
         self.reload_weights({"effects_encoder": args.ckpt_path_enc}, ddp=trained_w_ddp)
         self.save_args(args)
@@ -69,7 +70,7 @@ class FXencoder_Inference:
         paths = glob(os.path.join(self.target_dir, "**", "*.wav"), recursive=True)
         for step, path in enumerate(paths):
             print(f"\nInference step : {step + 1}/{len(paths)}\n---current file path : {path}---")
-            wav = load_wav_segment(path, axis=0)
+            wav = load_wav_segment(path, axis=0, sample_rate=self.sample_rate, convert=self.convert)
             if wav.ndim == 1:
                 wav = np.stack((wav, wav), axis=0)
             elif wav.shape[1] == 2:
@@ -78,6 +79,14 @@ class FXencoder_Inference:
             out = path.replace(self.target_dir, self.output_dir).replace(".wav", "_fx_embedding.npy")
             os.makedirs(os.path.dirname(out), exist_ok=True)
             np.save(out, emb)
+
+
+def str2bool(v):
+    if v.lower() in ("yes", "true", "t", "y", "1"):
+        return True
+    if v.lower() in ("no", "false", "f", "n", "0"):
+        return False
+    raise argparse.ArgumentTypeError("Boolean value expected.")
 
 
 def build_parser():
@@ -92,6 +101,8 @@ def build_parser():
     i.add_argument("--batch_size", type=int, default=1)
     i.add_argument("--inference_device", type=str, default="gpu")
     i.add_argument("--precision", type=str, default="fp32", choices=["fp32", "bf16"])
+    i.add_argument("--convert_input", type=str2bool, default=False,
+                   help="accept files at another sample rate (resampled to 44.1 kHz on the GPU) and 24-bit PCM; off: they raise")
     return p
 
 

@@ -268,6 +268,9 @@ def build_parser():
     i.add_argument("--normalization_order", type=str2bool, default=["loudness", "eq", "compression", "imager", "loudness"])
     i.add_argument("--interpolation", type=str2bool, default=False)
     i.add_argument("--interpolate_segments", type=int, default=30)
+    i.add_argument("--convert_input", type=str2bool, default=False,
+                   help="accept stems at another sample rate (resampled to --sample_rate on the GPU) and 24-bit PCM; off: they raise, "
+                        "like the reference.  Outputs are written at --sample_rate either way")
     v = p.add_argument_group("Device args")
     v.add_argument("--workers", type=int, default=1)
     v.add_argument("--inference_device", type=str, default="gpu")

@@ -1,5 +1,6 @@
 """Device calls under the input normaliser: thin typed wrappers over the C ABI (include/mst_hip.h) working on torch device
 tensors.  Host-side control flow lives in fx_utils.py / utils_data_normalization.py / normalization_imager.py."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -333,3 +334,94 @@ def biquad_cascade(x, sos):
         lib.check(lib.mst_fx_biquad_cascade(x.data_ptr(), y.data_ptr(), n, L, Cn, coef.ctypes.data_as(C.POINTER(C.c_double)), len(coef),
                                             sc.data_ptr(), nbytes, None, lib.stream_ptr(x)), "mst_fx_biquad_cascade")
     return y
+
+
+# ---------------------------------------------------------------------------------------- sample-rate conversion (csrc/resample_kernels.h)
+class Resampler:
+    """The polyphase resampler of one pair of rates: y[m] = sum_j h[m down - j up + half] x[j] (scipy.signal.resample_poly with
+    padtype='constant'), float64 sums of exact products rounded once to float32."""
+    _cache = {}
+
+    @classmethod
+    def get(cls, rate_in, rate_out):
+        lib = _lib.lib()
+        key = (lib.path, int(rate_in), int(rate_out))
+        if key not in cls._cache:
+            if len(cls._cache) > 8:
+                cls._cache.clear()
+            cls._cache[key] = cls(lib, rate_in, rate_out)
+        return cls._cache[key]
+
+    def __init__(self, lib, rate_in, rate_out):
+        self.lib, self.rate_in, self.rate_out = lib, int(rate_in), int(rate_out)
+        self._handles = {}
+        g = np.gcd(self.rate_in, self.rate_out) if self.rate_in > 0 and self.rate_out > 0 else 1
+        self.up, self.down = self.rate_out // int(g), self.rate_in // int(g)
+
+    def _handle(self, device=None):
+        """the handle on `device` (its tap table lives there); None: any handle there is - what info() and taps() ask is host data"""
+        if device is None and self._handles:
+            return next(iter(self._handles.values()))
+        key = str(device)
+        if key not in self._handles:
+            h = C.c_void_p()
+            on = torch.cuda.device(device) if device is not None and torch.device(device).type == "cuda" else contextlib.nullcontext()
+            with on:
+                self.lib.check(self.lib.mst_resample_create(self.rate_in, self.rate_out, C.byref(h)), "mst_resample_create")
+            self._handles[key] = h
+        return self._handles[key]
+
+    def info(self):
+        """(up, down, half_len, taps_per_phase)"""
+        v = [C.c_int() for _ in range(4)]
+        self.lib.check(self.lib.mst_resample_info(self._handle(), *[C.byref(a) for a in v]), "mst_resample_info")
+        return tuple(a.value for a in v)
+
+    def length(self, n_in):
+        """ceil(n_in * up / down): the frames a signal of n_in frames comes out with"""
+        return -((-int(n_in) * self.up) // self.down)
+
+    def taps(self):
+        """the 2 half_len + 1 float32 prototype taps as the library designed them"""
+        n = 2 * self.info()[2] + 1
+        out = np.empty(n, dtype=np.float32)
+        self.lib.check(self.lib.mst_resample_taps(self._handle(), out.ctypes.data_as(C.POINTER(C.c_float)), n), "mst_resample_taps")
+        return out
+
+    def forward(self, x, n_out=None, in_start=0, out_start=0):
+        """x device float32 [n, n_in, C] = inputs in_start .. of every item -> [n, n_out, C] = outputs out_start ..; the defaults resample
+        the whole signal"""
+        lib = self.lib
+        lib.require_device(x, "mst_resample_forward")
+        if x.dtype != torch.float32 or x.dim() != 3:
+            raise ValueError(f"mst_resample_forward: float32 [n, L, C] expected, got {x.dtype} {tuple(x.shape)}")
+        x = x.contiguous()
+        n, n_in, Cn = x.shape
+        n_out = self.length(n_in) if n_out is None else int(n_out)
+        y = torch.empty(n, n_out, Cn, dtype=torch.float32, device=x.device)
+        if n_in and n_out and n:
+            with lib.device_ctx(x):
+                lib.check(lib.mst_resample_forward(self._handle(x.device), x.data_ptr(), n_in, int(in_start), y.data_ptr(), n_out,
+                                                   int(out_start), n, Cn, lib.stream_ptr(x)), "mst_resample_forward")
+        else:
+            y.zero_()
+        return y
+
+    def __del__(self):
+        try:
+            for h in self._handles.values():
+                self.lib.mst_resample_destroy(h)
+        except Exception:
+            pass
+
+
+def resample(x, rate_in, rate_out):
+    """x float tensor [n, L, C] or [L, C], on the device or on the host (it then travels there and the result comes back) -> float32 of the same
+    rank at ceil(L * rate_out / rate_in) frames.  Equal rates: x as float32, nothing runs."""
+    t = x.to(torch.float32)
+    if int(rate_in) == int(rate_out):
+        return t
+    lib = _lib.lib()
+    y = Resampler.get(rate_in, rate_out).forward(_batch(lib.to_device(t)))
+    y = y[0] if x.dim() == 2 else y
+    return y if x.is_cuda else y.cpu()
