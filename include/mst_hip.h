@@ -50,7 +50,7 @@ typedef enum {
 
 #define MST_MAX_BLOCKS 32
 
-int mst_version(void);          /* 101: the mst_resample_* entry points */
+int mst_version(void);          /* 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
 const char *mst_last_error(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -319,11 +319,64 @@ size_t mst_fx_biquad_scratch_bytes(int n_items, long L, int C, int n_bands);
 int mst_fx_biquad_cascade(const float *x_dev, float *y_dev, int n_items, long L, int C, const double *coef_host,
                           int n_bands, double *scratch_dev, size_t scratch_bytes, const MstFxFuse *fuse, void *stream);
 
+/* DIAGNOSTIC (since mst_version() 102): what mst_fx_biquad_cascade does with a scratch buffer for this shape, and where its float64
+ * intermediates lie in that buffer after the call.  Host only, launches nothing.  The layout is an implementation detail: it may change
+ * with mst_version().  ends / starts: [n_items * C][nchunks][record_doubles] float64, state order (z1, z2) per band, the states beyond
+ * 2 * n_bands unused; ends = the zero-state end state of every FULL chunk of M samples (a short last chunk's record is zeros), starts =
+ * the true state at the start of every chunk.  time_parallel 0: the serial kernel runs (one chunk, or no band) and the buffer is unused. */
+typedef struct {
+    unsigned struct_size;        /* = sizeof(MstFxBiquadPlan) of the caller's header; another value: MST_ERR_ARG */
+    int time_parallel;
+    int M;                       /* samples per chunk */
+    int scan_threads;            /* 256 or 512: workgroup size of the scan over the chunk states (0: no scan) */
+    int record_doubles;          /* float64 values per chunk record */
+    long nchunks;
+    size_t ends_offset, starts_offset;      /* bytes from scratch_dev */
+} MstFxBiquadPlan;
+int mst_fx_biquad_plan(int n_items, long L, int C, int n_bands, MstFxBiquadPlan *plan);
+/* DIAGNOSTIC (since mst_version() 102), host only: the tables the time-parallel cascade of coef_host ([n_bands][6] as for
+ * mst_fx_biquad_cascade) uploads for chunk length M (a multiple of 16; MstFxBiquadPlan.M) - made by the very code the call runs -
+ * table_host [M][2 n_bands]: the state m steps after a unit impulse; powers_host [9][2 n_bands][2 n_bands] row-major: (A^M)^(2^l),
+ * l = 0 .. 8, A^M by the float64 recursion, squared up level by level. */
+int mst_fx_biquad_tables(const double *coef_host, int n_bands, int M, double *table_host, double *powers_host);
+
 /* Compressor.process / compressor_process (:529-587, :637-649), makeup gain 0.  With a scratch buffer of
  * mst_fx_compressor_scratch_bytes() (about 9 bytes per sample) the gain computer and the gain application run over all samples
  * in parallel and the attack/release smoother runs parallel in time (per-chunk convex piecewise-linear maps + one walk over the
- * chunk summaries of each sequence); scratch_dev = NULL runs the serial form, one wave per sequence. */
+ * chunk summaries of each sequence); scratch_dev = NULL runs the serial form, one wave per sequence.
+ * The time-parallel smoother runs only where its chunk maps are well conditioned: the pieces of a 32-step chunk map have slopes
+ * aA^(32-p) aR^p (aA, aR = exp(-1 / (0.001 sample_rate time_ms))), and the walk over the chunks loses kappa = (max / min)^32 of them in
+ * float64.  Beyond kappa_limit (MstFxCompressorPlan; about 6e5: at 44.1 kHz an attack below ~0.055 ms against a slow release) a plain call
+ * runs the serial form whatever the scratch buffer, and a call that form cannot serve - chain fusion (in_scale_dev / out_sumsq_dev), or
+ * mst_fx_compressor_grid - returns MST_ERR_UNSUPPORTED, the message naming the attack and release coefficients and the limit.
+ * kappa_limit = 6.07e5 - min(L, 1 / (1 - max(aA, aR))): it falls with the signal length and the slower time constant and is negative once
+ * both pass about 6e5 samples (a release above ~14 s at 44.1 kHz on a signal that long); every such call is serial or refused. */
 size_t mst_fx_compressor_scratch_bytes(int n_items, long L, int C);
+/* DIAGNOSTIC (since mst_version() 102): which form mst_fx_compressor / mst_fx_compressor_grid take for this shape and these times when given
+ * the scratch buffer, and where the intermediates lie in it after the call.  Host only, launches nothing; the layout may change with
+ * mst_version().  forms: MstFxFuse.forms of the call.
+ *   xl      [L][n_seq] float64 (SPLIT_SERIAL only; n_seq = n_items * C): the smoothed level y_l of every sample
+ *   maps    [n_seq][nchunks][record_doubles]: per 32-sample chunk b_0 (intercept of the all-attack piece), lb_1 .. lb_n (the sorted values at
+ *           which the pieces of the chunk's map meet, n = samples of the chunk), 1e300 beyond the chunk's pieces
+ *   ystart  [nchunks][n_seq]: the smoother's value at the start of every chunk
+ *   tab     [256]: unused by the call (the log10 table lives in a buffer of the library's)
+ *   carry   [n_seq]: the smoother's value behind the last sample (between two time slices: behind the slice)
+ *   tsums   per 64-sample tile: [tile][n_items][3] = sum y^2, sum (l + r)^2, sum (l - r)^2 with out_ms_dev, else [tile][n_seq] = sum y^2
+ * Time slice i of nslices covers the chain batches (32 chunks each) nbatch * i / nslices .. nbatch * (i + 1) / nslices - 1. */
+#define MST_FX_COMP_SPLIT_SERIAL 0     /* fewer than four chunks: gain / smoother / apply kernels, one lane per sequence in the smoother */
+#define MST_FX_COMP_TIME_PARALLEL 1    /* chunk maps, chain walk, apply */
+#define MST_FX_COMP_WAVE_SERIAL 2      /* kappa > kappa_limit: one wave per sequence, no scratch use; fusion and grid calls are refused */
+typedef struct {
+    unsigned struct_size;        /* = sizeof(MstFxCompressorPlan) of the caller's header; another value: MST_ERR_ARG */
+    int form;                    /* MST_FX_COMP_* */
+    int nslices;
+    int record_doubles;          /* float64 values per chunk record of maps */
+    long nchunks, nbatch, ntiles;
+    double kappa, kappa_limit;
+    size_t xl_offset, maps_offset, ystart_offset, tab_offset, carry_offset, tsums_offset, total_bytes;      /* bytes from scratch_dev */
+} MstFxCompressorPlan;
+int mst_fx_compressor_plan(int n_items, long L, int C, double attack_ms, double release_ms, double sample_rate, int forms,
+                           MstFxCompressorPlan *plan);
 int mst_fx_compressor(const float *x_dev, float *y_dev, int n_items, long L, int C, double threshold_db,
                       double attack_ms, double release_ms, double ratio, double sample_rate, double *scratch_dev,
                       size_t scratch_bytes, const MstFxFuse *fuse, void *stream);

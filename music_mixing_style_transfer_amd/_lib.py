@@ -45,6 +45,29 @@ class MstFxFuse(C.Structure):
                          out_ms_dev, in_ms_dev)
 
 
+FX_COMP_SPLIT_SERIAL, FX_COMP_TIME_PARALLEL, FX_COMP_WAVE_SERIAL = 0, 1, 2      # MstFxCompressorPlan.form
+
+
+class MstFxBiquadPlan(C.Structure):
+    """include/mst_hip.h MstFxBiquadPlan (diagnostic; the layout may change with mst_version())."""
+    _fields_ = [("struct_size", C.c_uint), ("time_parallel", C.c_int), ("M", C.c_int), ("scan_threads", C.c_int), ("record_doubles", C.c_int),
+                ("nchunks", C.c_long), ("ends_offset", C.c_size_t), ("starts_offset", C.c_size_t)]
+
+    def __init__(self):
+        super().__init__(C.sizeof(MstFxBiquadPlan))
+
+
+class MstFxCompressorPlan(C.Structure):
+    """include/mst_hip.h MstFxCompressorPlan (diagnostic; the layout may change with mst_version())."""
+    _fields_ = [("struct_size", C.c_uint), ("form", C.c_int), ("nslices", C.c_int), ("record_doubles", C.c_int), ("nchunks", C.c_long),
+                ("nbatch", C.c_long), ("ntiles", C.c_long), ("kappa", C.c_double), ("kappa_limit", C.c_double), ("xl_offset", C.c_size_t),
+                ("maps_offset", C.c_size_t), ("ystart_offset", C.c_size_t), ("tab_offset", C.c_size_t), ("carry_offset", C.c_size_t),
+                ("tsums_offset", C.c_size_t), ("total_bytes", C.c_size_t)]
+
+    def __init__(self):
+        super().__init__(C.sizeof(MstFxCompressorPlan))
+
+
 class MstEncDesc(C.Structure):
     _fields_ = [("nblocks", C.c_int), ("channels", C.c_int * (MST_MAX_BLOCKS + 1)), ("kernels", C.c_int * MST_MAX_BLOCKS),
                 ("strides", C.c_int * MST_MAX_BLOCKS), ("dilations", C.c_int * MST_MAX_BLOCKS), ("valid_padding", C.c_int), ("act_slope", C.c_float)]
@@ -104,6 +127,9 @@ SIGNATURES = {
     "mst_film_forward": (C.c_int, [_F, _F, _F, C.c_int, C.c_int, C.c_int, _F, _F, C.c_int, C.c_long, _F, _P]),
     "mst_embedding_mean": (C.c_int, [_F, C.c_int, C.c_int, _F, _P]),
     "mst_fx_biquad_scratch_bytes": (C.c_size_t, [C.c_int, C.c_long, C.c_int, C.c_int]),
+    "mst_fx_biquad_plan": (C.c_int, [C.c_int, C.c_long, C.c_int, C.c_int, C.POINTER(MstFxBiquadPlan)]),
+    "mst_fx_biquad_tables": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "mst_fx_compressor_plan": (C.c_int, [C.c_int, C.c_long, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(MstFxCompressorPlan)]),
     "mst_fx_biquad_cascade": (C.c_int, [_F, _F, C.c_int, C.c_long, C.c_int, C.POINTER(C.c_double), C.c_int, _P, C.c_size_t, _P, _P]),
     "mst_fx_sumsq": (C.c_int, [_F, C.c_int, C.c_long, _P, _P]),
     "mst_fx_rms_pending": (C.c_int, [_P, _P, C.c_long, _P, C.c_long, _P, C.c_int, _P]),

@@ -41,6 +41,9 @@ int biquad_chunk(long L, long n_seq) {
     }
     return best_m;
 }
+// what mst_fx_biquad_cascade does with a scratch buffer, and the workgroup size of its scan: shared with mst_fx_biquad_plan
+bool biquad_time_parallel(long nchunks, int n_bands) { return nchunks > 1 && n_bands > 0; }
+int biquad_scan_threads(long nchunks) { return nchunks > 255 ? 512 : 256; }
 void biquad_coefs(const double *coef, int n_bands, double (*out)[5]) {
     for (int k = 0; k < MST_MAX_BANDS; ++k)
         for (int i = 0; i < 5; ++i) out[k][i] = 0.0;
@@ -56,6 +59,47 @@ void biquad_coefs(const double *coef, int n_bands, double (*out)[5]) {
 }  // namespace
 
 namespace {
+// The host-side tables of a coefficient set at chunk length M, [M][S] impulse states | [levels][S][S] powers (A^M)^(2^l) | A fragments: what
+// biquad_impulse_table uploads and mst_fx_biquad_tables shows
+void biquad_host_tables(const double (*coef)[5], int n_bands, int M, double *host) {
+    const int S = 2 * n_bands;
+    const size_t n_tab = (size_t)M * S, n_pow = (size_t)MST_BIQUAD_LEVELS * S * S, n_frag = (size_t)((M + 15) / 16) * 4 * 64;
+    std::vector<double> z(S, 0.0);
+    for (int m = 0; m < M; ++m) {
+        double v = m == 0 ? 1.0 : 0.0;
+        for (int b = 0; b < n_bands; ++b) v = fx_biquad_band(v, z[2 * b], z[2 * b + 1], coef[b]);
+        for (int j = 0; j < S; ++j) host[(size_t)m * S + j] = z[j];
+    }
+    {   // A^M column by column (the cascade run M steps on zero input from each unit state), then squared up level by level
+        double *pm = host + n_tab;
+        for (int col = 0; col < S; ++col) {
+            std::vector<double> u(S, 0.0);
+            u[col] = 1.0;
+            for (int n = 0; n < M; ++n) {
+                double v = 0.0;
+                for (int b = 0; b < n_bands; ++b) v = fx_biquad_band(v, u[2 * b], u[2 * b + 1], coef[b]);
+            }
+            for (int row = 0; row < S; ++row) pm[(size_t)row * S + col] = u[row];
+        }
+        for (int l = 1; l < MST_BIQUAD_LEVELS; ++l) {
+            const double *cur = pm + (size_t)(l - 1) * S * S;
+            double *nxt = pm + (size_t)l * S * S;
+            for (int r = 0; r < S; ++r)
+                for (int c = 0; c < S; ++c) {
+                    double acc = 0.0;
+                    for (int j = 0; j < S; ++j) acc += cur[r * S + j] * cur[j * S + c];
+                    nxt[r * S + c] = acc;
+                }
+        }
+    }
+    {   // fragment (slab sb, k-step kk), lane (state j = l & 15, kq = l >> 4): the weight of sample 16 sb + 4 kk + kq in the end state, h_(M - 1 - sample)[j]
+        double *fr = host + n_tab + n_pow;
+        for (size_t i = 0; i < n_frag; ++i) {
+            const int l = (int)(i % 64), kk = (int)(i / 64 % 4), sb = (int)(i / 256), j = l & 15, smp = 16 * sb + 4 * kk + (l >> 4);
+            fr[i] = (j < S && smp < M) ? host[(size_t)(M - 1 - smp) * S + j] : 0.0;
+        }
+    }
+}
 // Impulse-state table of a biquad cascade for fx_biquad_ends_kernel: h_m = the cascade's state m steps after a unit impulse, m = 0 .. M - 1,
 // [M][2 * n_bands] float64.  Built on the host (the kernels' own recursion) and kept on the device per (device, coefficients, M): a chain calls
 // its equaliser with the same settings again and again.  An entry owns its host copy (the asynchronous upload reads it) and its device
@@ -109,41 +153,7 @@ const double *biquad_impulse_table(const double (*coef)[5], int n_bands, int M, 
         t->devp = nullptr;
         t->host.assign(n_all, 0.0);
     }
-    std::vector<double> z(S, 0.0);
-    for (int m = 0; m < M; ++m) {
-        double v = m == 0 ? 1.0 : 0.0;
-        for (int b = 0; b < n_bands; ++b) v = fx_biquad_band(v, z[2 * b], z[2 * b + 1], coef[b]);
-        for (int j = 0; j < S; ++j) t->host[(size_t)m * S + j] = z[j];
-    }
-    {   // A^M column by column (the cascade run M steps on zero input from each unit state), then squared up level by level
-        double *pm = t->host.data() + n_tab;
-        for (int col = 0; col < S; ++col) {
-            std::vector<double> u(S, 0.0);
-            u[col] = 1.0;
-            for (int n = 0; n < M; ++n) {
-                double v = 0.0;
-                for (int b = 0; b < n_bands; ++b) v = fx_biquad_band(v, u[2 * b], u[2 * b + 1], coef[b]);
-            }
-            for (int row = 0; row < S; ++row) pm[(size_t)row * S + col] = u[row];
-        }
-        for (int l = 1; l < MST_BIQUAD_LEVELS; ++l) {
-            const double *cur = pm + (size_t)(l - 1) * S * S;
-            double *nxt = pm + (size_t)l * S * S;
-            for (int r = 0; r < S; ++r)
-                for (int c = 0; c < S; ++c) {
-                    double acc = 0.0;
-                    for (int j = 0; j < S; ++j) acc += cur[r * S + j] * cur[j * S + c];
-                    nxt[r * S + c] = acc;
-                }
-        }
-    }
-    {   // fragment (slab sb, k-step kk), lane (state j = l & 15, kq = l >> 4): the weight of sample 16 sb + 4 kk + kq in the end state, h_(M - 1 - sample)[j]
-        double *fr = t->host.data() + n_tab + n_pow;
-        for (size_t i = 0; i < n_frag; ++i) {
-            const int l = (int)(i % 64), kk = (int)(i / 64 % 4), sb = (int)(i / 256), j = l & 15, smp = 16 * sb + 4 * kk + (l >> 4);
-            fr[i] = (j < S && smp < M) ? t->host[(size_t)(M - 1 - smp) * S + j] : 0.0;
-        }
-    }
+    biquad_host_tables(coef, n_bands, M, t->host.data());
     if (!t->devp && hipMalloc((void **)&t->devp, t->host.size() * sizeof(double)) != hipSuccess) {
         t->dev = -1;
         t->devp = nullptr;
@@ -168,6 +178,34 @@ extern "C" size_t mst_fx_biquad_scratch_bytes(int n_items, long L, int C, int n_
     return (2 * states + (size_t)MST_BIQUAD_LEVELS * 4 * MST_MAX_BANDS * MST_MAX_BANDS) * sizeof(double);      // ends | starts | (A^M)^(2^l)
 }
 
+extern "C" int mst_fx_biquad_plan(int n_items, long L, int C, int n_bands, MstFxBiquadPlan *plan) {
+    if (!plan || plan->struct_size != sizeof(MstFxBiquadPlan)) return fail(MST_ERR_ARG, "mst_fx_biquad_plan: MstFxBiquadPlan.struct_size does not match this library's layout");
+    if (n_items < 1 || L < 1 || C < 1 || n_bands < 0 || n_bands > MST_MAX_BANDS) return fail(MST_ERR_ARG, "mst_fx_biquad_plan: bad argument");
+    const int M = biquad_chunk(L, (long)n_items * C);
+    const long nchunks = (L + M - 1) / M;
+    plan->M = M;
+    plan->nchunks = nchunks;
+    plan->time_parallel = biquad_time_parallel(nchunks, n_bands);            // what mst_fx_biquad_cascade does when it is given the scratch buffer
+    plan->scan_threads = plan->time_parallel ? biquad_scan_threads(nchunks) : 0;
+    plan->record_doubles = 2 * MST_MAX_BANDS;
+    plan->ends_offset = 0;
+    plan->starts_offset = (size_t)n_items * C * nchunks * 2 * MST_MAX_BANDS * sizeof(double);
+    return MST_OK;
+}
+
+extern "C" int mst_fx_biquad_tables(const double *coef, int n_bands, int M, double *table_host, double *powers_host) {
+    if (!coef || !table_host || !powers_host || n_bands < 1 || n_bands > MST_MAX_BANDS || M < 16 || M % 16) return fail(MST_ERR_ARG, "mst_fx_biquad_tables: bad argument");
+    double cf[MST_MAX_BANDS][5];
+    biquad_coefs(coef, n_bands, cf);
+    const int S = 2 * n_bands;
+    const size_t n_tab = (size_t)M * S, n_pow = (size_t)MST_BIQUAD_LEVELS * S * S, n_frag = (size_t)((M + 15) / 16) * 4 * 64;
+    std::vector<double> host(n_tab + n_pow + n_frag, 0.0);
+    biquad_host_tables(cf, n_bands, M, host.data());
+    std::memcpy(table_host, host.data(), n_tab * sizeof(double));
+    std::memcpy(powers_host, host.data() + n_tab, n_pow * sizeof(double));
+    return MST_OK;
+}
+
 extern "C" int mst_fx_biquad_cascade(const float *x, float *y, int n_items, long L, int C, const double *coef, int n_bands,
                                      double *scratch, size_t scratch_bytes, const MstFxFuse *fuse, void *stream) {
     if (!x || !y || !coef || n_items < 1 || L < 1 || C < 1) return fail(MST_ERR_ARG, "mst_fx_biquad_cascade: bad argument");
@@ -179,7 +217,7 @@ extern "C" int mst_fx_biquad_cascade(const float *x, float *y, int n_items, long
     if (n_bands < 0 || n_bands > MST_MAX_BANDS) return fail(MST_ERR_UNSUPPORTED, "mst_fx_biquad_cascade: at most 8 bands");
     const int M = biquad_chunk(L, (long)n_items * C);
     const long nchunks = (L + M - 1) / M;
-    if (scratch && nchunks > 1 && n_bands > 0) {
+    if (scratch && biquad_time_parallel(nchunks, n_bands)) {
         if (scratch_bytes < mst_fx_biquad_scratch_bytes(n_items, L, C, n_bands))
             return fail(MST_ERR_WORKSPACE, "mst_fx_biquad_cascade: scratch too small");
         BiquadChunkArgs a;
@@ -264,7 +302,7 @@ extern "C" int mst_fx_biquad_cascade(const float *x, float *y, int n_items, long
                 default: MST_LAUNCH((fx_biquad_scan_kernel<8, nb>), sg, dim3(nb), stream, e, starts, pmc, a.n_seq, (int)nchunks); break;
             }
         };
-        if (nchunks > 255) launch_scan(std::integral_constant<int, 512>{});
+        if (biquad_scan_threads(nchunks) == 512) launch_scan(std::integral_constant<int, 512>{});
         else launch_scan(std::integral_constant<int, 256>{});
         MST_CHECK_LAUNCH("fx_biquad_scan_kernel");
         if (C == 2 && !eq_lane_apply) {          // stereo: the chunks travel in 16-frame slabs through LDS, in and out
@@ -326,6 +364,66 @@ extern "C" size_t mst_fx_compressor_scratch_bytes(int n_items, long L, int C) {
 }
 
 namespace {
+// Conditioning of the time-parallel smoother ("FX passes").  The pieces of a chunk's map have slopes aA^(T-p) aR^p; the
+// chain walk rebuilds intercepts and crossing inputs from the stored values by dividing by those slopes, so its start values carry the
+// rounding of the stored values times kappa_T = (largest / smallest slope) = (max(aA, aR) / min(aA, aR))^T.  The start-value bound
+//     C_START 2^-53 max|x_l| (min(L, 1 / (1 - max(aA, aR))) + kappa_T)
+// times ln 10 / 20 (level -> relative gain) has to stay at or below 2^-27, a quarter of a float32 output ulp, with max|x_l| = 120 dB (the
+// level difference of any sample between 1e-6 and 1e6 at any threshold in that range).  Beyond that the serial forms run.  The reach grows with L
+// and the slower time constant: past about 6e5 samples of both (a release above ~14 s at 44.1 kHz on a signal that long - far outside any
+// processor's range) the limit is negative and every such call is serial or refused whatever kappa: the recursion's own rounding has then used
+// the quarter ulp up.
+constexpr double FX_COMP_C_START = 8.0;
+constexpr double FX_COMP_XL_MAX = 120.0;
+double comp_kappa(double aA, double aR) {
+    const double lo = std::min(aA, aR), hi = std::max(aA, aR);
+    return lo > 0.0 ? std::pow(hi / lo, MST_COMP_T) : HUGE_VAL;
+}
+double comp_kappa_limit(double aA, double aR, long L) {
+    const double amax = std::max(aA, aR);
+    const double reach = amax < 1.0 ? std::min((double)L, 1.0 / (1.0 - amax)) : (double)L;
+    return 0x1p-27 / (FX_COMP_C_START * 0x1p-53 * FX_COMP_XL_MAX * 0.11512925464970228420) - reach;
+}
+bool comp_well_conditioned(double aA, double aR, long L) { return comp_kappa(aA, aR) <= comp_kappa_limit(aA, aR, L); }
+double comp_alpha(double sample_rate, double ms) { return std::exp(-1.0 / (0.001 * sample_rate * ms)); }
+constexpr int FX_SLICES = 3;    // time slices of a large compressor call (compressor_run; measured: 0.523-0.539 ms per chain with 3, 0.540-0.550 with 4, 0.556-0.580 with 2, 0.67 with 8; profiles/r05_fx_slices_ab.txt)
+int comp_slices(int nbatch, long n_seq, long L, bool slice_small) {
+    return ((nbatch >= 32 && (double)n_seq * (double)L >= 4.0e6) || (slice_small && nbatch >= 8)) ? FX_SLICES : 1;
+}
+std::string comp_refusal(const char *who, double aA, double aR, long L) {
+    char buf[320];
+    std::snprintf(buf, sizeof(buf), "%s: attack / release coefficients %.6g / %.6g spread the chunk maps' slopes by kappa = %.3g, beyond the limit %.3g of "
+                  "the time-parallel smoother; this call (chain fusion or parameter grid) has no serial form - use plain mst_fx_compressor calls",
+                  who, aA, aR, comp_kappa(aA, aR), comp_kappa_limit(aA, aR, L));
+    return buf;
+}
+}  // namespace
+
+extern "C" int mst_fx_compressor_plan(int n_items, long L, int C, double attack_ms, double release_ms, double sample_rate, int forms,
+                                      MstFxCompressorPlan *plan) {
+    if (!plan || plan->struct_size != sizeof(MstFxCompressorPlan)) return fail(MST_ERR_ARG, "mst_fx_compressor_plan: MstFxCompressorPlan.struct_size does not match this library's layout");
+    if (n_items < 1 || L < 1 || C < 1 || attack_ms <= 0 || release_ms <= 0 || sample_rate <= 0) return fail(MST_ERR_ARG, "mst_fx_compressor_plan: bad argument");
+    const CompScratch cs = comp_scratch(n_items, L, C);
+    const double aA = comp_alpha(sample_rate, attack_ms), aR = comp_alpha(sample_rate, release_ms);
+    plan->nchunks = cs.nchunks;
+    plan->nbatch = (cs.nchunks + MST_CHAIN_CB - 1) / MST_CHAIN_CB;
+    plan->ntiles = cs.ntiles;
+    plan->kappa = comp_kappa(aA, aR);
+    plan->kappa_limit = comp_kappa_limit(aA, aR, L);
+    plan->form = cs.nchunks < 4 ? MST_FX_COMP_SPLIT_SERIAL : (plan->kappa <= plan->kappa_limit ? MST_FX_COMP_TIME_PARALLEL : MST_FX_COMP_WAVE_SERIAL);
+    plan->nslices = plan->form == MST_FX_COMP_TIME_PARALLEL ? comp_slices((int)plan->nbatch, (long)n_items * C, L, (forms & MST_FX_FORM_COMP_SLICE_SMALL) != 0) : 1;
+    plan->record_doubles = MST_COMP_REC;
+    plan->xl_offset = 0;
+    plan->maps_offset = cs.xl;
+    plan->ystart_offset = cs.xl + cs.maps;
+    plan->tab_offset = cs.xl + cs.maps + cs.ystart;
+    plan->carry_offset = plan->tab_offset + cs.tab;
+    plan->tsums_offset = plan->carry_offset + cs.carry;
+    plan->total_bytes = cs.total;
+    return MST_OK;
+}
+
+namespace {
 // fx_log10_table_kernel's 256 doubles, one copy per device, made by the first compressor call there (kept for the life of the process)
 const double *log10_table(void *stream) {
     static std::mutex mu;
@@ -353,7 +451,6 @@ struct FxSide {
     hipEvent_t fork = nullptr, join = nullptr, map_done[8] = {}, chain_done[8] = {};
     std::mutex mu;
 };
-constexpr int FX_SLICES = 3;    // time slices of a large compressor call (measured: 0.523-0.539 ms per chain with 3, 0.540-0.550 with 4, 0.556-0.580 with 2, 0.67 with 8; profiles/r05_fx_slices_ab.txt)
 FxSide *fx_side() {
     static std::mutex mu;
     static FxSide *sides[64] = {};
@@ -380,7 +477,12 @@ FxSide *fx_side() {
 }
 
 int compressor_run(CompArgs a, int n_items, long L, int C, double *scratch, size_t scratch_bytes, void *stream, bool slice_small = false) {
-    if (!scratch) {
+    // the time-parallel smoother only where its chunk maps are well conditioned (one host comparison, comp_well_conditioned); beyond, the plain
+    // call runs one wave per sequence; a call that form cannot serve (chain fusion, parameter grid) is refused, never answered with garbage
+    const bool serial_only = (L + MST_COMP_T - 1) / MST_COMP_T >= 4 && !comp_well_conditioned(a.alpha_att, a.alpha_rel, L);
+    if (serial_only && (a.thr_items || a.in_scale || a.out_sumsq))
+        return fail(MST_ERR_UNSUPPORTED, comp_refusal(a.thr_items ? "mst_fx_compressor_grid" : "mst_fx_compressor", a.alpha_att, a.alpha_rel, L));
+    if (!scratch || serial_only) {
         MST_LAUNCH(fx_compressor_kernel, dim3((a.n_seq + 3) / 4), dim3(256), stream, a);
         MST_CHECK_LAUNCH("fx_compressor_kernel");
         return MST_OK;
@@ -442,7 +544,7 @@ int compressor_run(CompArgs a, int n_items, long L, int C, double *scratch, size
     //  EXPERIMENTS.md section E.3, tools/proto/r06_fx_*.)
     const int nbatch = (int)((cs.nchunks + MST_CHAIN_CB - 1) / MST_CHAIN_CB);
     const int gy = (a.n_seq + 63) / 64;
-    int ns = ((nbatch >= 32 && (double)a.n_seq * (double)L >= 4.0e6) || (slice_small && nbatch >= 8)) ? FX_SLICES : 1;
+    int ns = comp_slices(nbatch, a.n_seq, L, slice_small);
     FxSide *side = ns > 1 ? fx_side() : nullptr;
     if (!side) ns = 1;
     auto launch_map = [&](int b0, int b1, void *st) -> int {
@@ -535,8 +637,8 @@ extern "C" int mst_fx_compressor(const float *x, float *y, int n_items, long L, 
     a.L = L;
     a.threshold = threshold_db;
     a.ratio = ratio;
-    a.alpha_att = std::exp(-1.0 / (0.001 * sample_rate * attack_ms));
-    a.alpha_rel = std::exp(-1.0 / (0.001 * sample_rate * release_ms));
+    a.alpha_att = comp_alpha(sample_rate, attack_ms);
+    a.alpha_rel = comp_alpha(sample_rate, release_ms);
     a.makeup = 0.0;
     a.in_scale = fuse ? fuse->in_scale_dev : nullptr;
     a.out_sumsq = fuse ? fuse->out_sumsq_dev : nullptr;
@@ -565,8 +667,8 @@ extern "C" int mst_fx_compressor_grid(const float *x, float *y, int n_items, lon
     a.thr_items = threshold_db_dev;
     a.ratio_items = ratio_dev;
     a.shared_x = 1;
-    a.alpha_att = std::exp(-1.0 / (0.001 * sample_rate * attack_ms));
-    a.alpha_rel = std::exp(-1.0 / (0.001 * sample_rate * release_ms));
+    a.alpha_att = comp_alpha(sample_rate, attack_ms);
+    a.alpha_rel = comp_alpha(sample_rate, release_ms);
     a.makeup = 0.0;
     int rc;
     if ((rc = compressor_run(a, n_items, L, C, scratch, scratch_bytes, stream))) return rc;

@@ -170,6 +170,20 @@ def compressor_grid(x, thresholds, ratios, attack_ms, release_ms, sample_rate, c
     ra = torch.tensor(ratios, dtype=torch.float64, device=dev)
     y = torch.empty(n, L, Cn, dtype=torch.float32, device=dev)
     with lib.device_ctx(x):
+        plan = _lib.MstFxCompressorPlan()
+        lib.check(lib.mst_fx_compressor_plan(n, L, Cn, float(attack_ms), float(release_ms), float(sample_rate), 0, C.byref(plan)),
+                  "mst_fx_compressor_plan")
+        if plan.form == _lib.FX_COMP_WAVE_SERIAL:
+            # attack / release beyond the time-parallel smoother's conditioning limit: the grid launch is refused there; every candidate
+            # runs as a plain serial call on the shared signal (rare: far outside the normaliser's own settings)
+            xc = x.contiguous()
+            for i, (t_db, r) in enumerate(zip(thresholds, ratios)):
+                t_db = 1.0 if float(r) == 1.0 else float(t_db)      # ratio 1 never reads the threshold; (0 dB, 1) would mean "bypass" to mst_fx_compressor
+                lib.check(lib.mst_fx_compressor(xc.data_ptr(), y[i].data_ptr(), 1, L, Cn, t_db, float(attack_ms), float(release_ms), float(r),
+                                                float(sample_rate), None, 0, None, lib.stream_ptr(x)), "mst_fx_compressor")
+                if clip and float(peaks(y[i:i + 1])[0]) >= 1.0:
+                    y[i].clamp_(-1.0, 1.0)
+            return y
         nbytes = lib.mst_fx_compressor_scratch_bytes(n, L, Cn)
         sc = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
         pk = torch.empty(n * 64, dtype=torch.float64, device=dev) if clip else None

@@ -251,7 +251,14 @@ class Compressor(Processor):
 
     def fusable(self, d):
         p = self.parameters
-        return not (p.threshold.value == 0.0 and p.ratio.value == 1.0)
+        if p.threshold.value == 0.0 and p.ratio.value == 1.0:
+            return False
+        # an attack / release pair beyond the time-parallel smoother's conditioning limit runs the serial form, which takes no part in
+        # the chain fusion (the library refuses such a fused call): the chain then materialises its input and calls process()
+        plan = _lib.MstFxCompressorPlan()
+        d.lib.check(d.lib.mst_fx_compressor_plan(d.n, d.L, d.C, float(p.attack_time.value), float(p.release_time.value),
+                                                 float(self.sample_rate), 0, C.byref(plan)), "mst_fx_compressor_plan")
+        return plan.form != _lib.FX_COMP_WAVE_SERIAL
 
     def _run(self, d, in_scale, want_sumsq):
         p = self.parameters
