@@ -50,7 +50,7 @@ typedef enum {
 
 #define MST_MAX_BLOCKS 32
 
-int mst_version(void);          /* 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
+int mst_version(void);          /* 103: per-item FX parameters, mst_fx_biquad_cascade_items / mst_fx_compressor_items / mst_fx_midside_imager_items / mst_fx_gain_items; 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
 const char *mst_last_error(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -340,6 +340,28 @@ int mst_fx_biquad_plan(int n_items, long L, int C, int n_bands, MstFxBiquadPlan 
  * l = 0 .. 8, A^M by the float64 recursion, squared up level by level. */
 int mst_fx_biquad_tables(const double *coef_host, int n_bands, int M, double *table_host, double *powers_host);
 
+/* PER-ITEM PARAMETERS (since mst_version() 103).  mst_fx_biquad_cascade with a coefficient set per item, in the launches of the shared call
+ * plus one: coef_dev is DEVICE float64 [n_items][n_bands][6], rows in coef_host's order (b0 b1 b2 a0 a1 a2); n_bands is common to the
+ * batch.  A launch on the caller's stream builds every item's tables on the device - the impulse states [M][2 n_bands] and the powers
+ * (A^M)^(2^l), l = 0 .. 8 - with M the chunk length of the shared call on this shape (the state pass of stereo audio is the VALU one for
+ * every item: no A-fragment image; MST_FX_FORM_EQ_VALU_ENDS changes nothing here): no host build, no upload, no cache entry, no mutex, no synchronisation, nothing the stream does not order.  The tables are
+ * the bits mst_fx_biquad_tables returns for the item's coefficients, and item i's output and by-products are the bits of
+ * mst_fx_biquad_cascade on the same batch with item i's coefficients.  scratch_dev: mst_fx_biquad_items_scratch_bytes(); it starts
+ * with the shared call's layout (ends / starts where mst_fx_biquad_plan says), the per-item tables lie behind
+ * (mst_fx_biquad_items_plan).  fuse: as mst_fx_biquad_cascade (in_scale_dev, out_sumsq_dev, out_in_sumsq_dev, the EQ forms).
+ * scratch_dev = NULL or a single chunk: the serial kernel with per-item coefficients (no fusion).  n_items <= 65535. */
+size_t mst_fx_biquad_items_scratch_bytes(int n_items, long L, int C, int n_bands);
+int mst_fx_biquad_cascade_items(const float *x_dev, float *y_dev, int n_items, long L, int C, const double *coef_dev, int n_bands,
+                                double *scratch_dev, size_t scratch_bytes, const MstFxFuse *fuse, void *stream);
+/* DIAGNOSTIC, host only: where mst_fx_biquad_cascade_items leaves item i's tables - at tables_offset + i * item_stride bytes from
+ * scratch_dev: [M][2 n_bands] impulse states, at + powers_offset [9][2 n_bands][2 n_bands] powers, at + coef_offset [8][5] b0 b1 b2 a1 a2 over a0 (zeros beyond n_bands).  The layout may change with mst_version(). */
+typedef struct {
+    unsigned struct_size;        /* = sizeof(MstFxBiquadItemsPlan) of the caller's header; another value: MST_ERR_ARG */
+    int M;                       /* samples per chunk: MstFxBiquadPlan.M of the same shape */
+    size_t tables_offset, item_stride, powers_offset, coef_offset, total_bytes;      /* bytes */
+} MstFxBiquadItemsPlan;
+int mst_fx_biquad_items_plan(int n_items, long L, int C, int n_bands, MstFxBiquadItemsPlan *plan);
+
 /* Compressor.process / compressor_process (:529-587, :637-649), makeup gain 0.  With a scratch buffer of
  * mst_fx_compressor_scratch_bytes() (about 9 bytes per sample) the gain computer and the gain application run over all samples
  * in parallel and the attack/release smoother runs parallel in time (per-chunk convex piecewise-linear maps + one walk over the
@@ -380,9 +402,31 @@ int mst_fx_compressor_plan(int n_items, long L, int C, double attack_ms, double 
 int mst_fx_compressor(const float *x_dev, float *y_dev, int n_items, long L, int C, double threshold_db,
                       double attack_ms, double release_ms, double ratio, double sample_rate, double *scratch_dev,
                       size_t scratch_bytes, const MstFxFuse *fuse, void *stream);
+/* The compressor with threshold, attack, release and ratio PER ITEM (since mst_version() 103), in the launches of mst_fx_compressor: the same
+ * forms (split-serial below four chunks, time-parallel, time slices), the scratch buffer and its layout are mst_fx_compressor's
+ * (mst_fx_compressor_scratch_bytes, mst_fx_compressor_plan), fusion as there including out_ms_dev; per-item x.  One batch may mix items with
+ * attack slower and faster than release and ratios above, below and equal to 1.  Item i gets the bits of mst_fx_compressor on the same batch
+ * with item i's settings.
+ * mst_fx_compressor_items_prepare (host only, launches nothing) fills the table the call reads - table_host, of
+ * mst_fx_compressor_items_table_bytes(n_items), meant to be pinned and uploaded without waiting - from params_host [n_items][4] = threshold
+ * dB, attack ms, release ms, ratio, with the functions the shared call uses: per item threshold and ratio (the curve), the attack / release
+ * coefficients and the two slope / inverse-slope rows of the chunk maps.  It applies mst_fx_compressor_plan's kappa_limit rule per item: an
+ * item beyond it makes the call return MST_ERR_UNSUPPORTED - the message names the item, its coefficients and the limit - and writes its index
+ * to first_refused_item (else -1); run such an item alone through mst_fx_compressor.  The bypass pair (threshold 0, ratio 1) is refused the same
+ * way.  table_dev must come from a successful prepare for the same n_items, L, C.  scratch_dev = NULL: the serial kernel. */
+size_t mst_fx_compressor_items_table_bytes(int n_items);
+int mst_fx_compressor_items_prepare(const double *params_host, int n_items, long L, int C, double sample_rate, int forms,
+                                    double *table_host, size_t table_bytes, int *first_refused_item);
+int mst_fx_compressor_items(const float *x_dev, float *y_dev, int n_items, long L, int C, const double *table_dev, double *scratch_dev,
+                            size_t scratch_bytes, const MstFxFuse *fuse, void *stream);
 /* MidSideImager.process (:964-1007), stereo only; scratch_dev: >= n_items * 2 * MST_SUMSQ_SLOTS doubles (partial energy sums) */
 int mst_fx_midside_imager(const float *x_dev, float *y_dev, int n_items, long L, double bal, double *scratch_dev,
                           const MstFxFuse *fuse, void *stream);
+/* The imager with a balance per item (since mst_version() 103): bal_dev is DEVICE float64 [n_items], rounded to three places on the device
+ * like the shared call does on the host.  post_gain_dev: DEVICE float32 [n_items], the per-item gain of the tail folding (fuse->post_rms);
+ * NULL: fuse->post_gain for every item.  Everything else as mst_fx_midside_imager, whose bits item i gets for bal_dev[i]. */
+int mst_fx_midside_imager_items(const float *x_dev, float *y_dev, int n_items, long L, const double *bal_dev, double *scratch_dev,
+                                const float *post_gain_dev, const MstFxFuse *fuse, void *stream);
 /* Haas.process / haas_process (:768-786, :826-843): y = x, y[:, wet] += feedback * np.roll(x[:, wet], delay) - the roll is
  * circular, delay may be negative; wet_channel 0 = 'left', 1 = 'right'.  c_in = 1 (mono, repeated to stereo) or 2;
  * y is always [n_items, L, 2]. */
@@ -408,6 +452,10 @@ int mst_fx_convolve(MstConvolver *cv, const float *x_dev, const float *h_dev, lo
 /* Gain.process (:1041-1051) */
 int mst_fx_gain(const float *x_dev, float *y_dev, int n_items, long L, int C, double gain_db, int invert, const MstFxFuse *fuse,
                 void *stream);
+/* Gain with a value per item (since mst_version() 103): gain_db_dev DEVICE float64 [n_items], invert_dev DEVICE int [n_items] (NULL: none
+ * inverted).  The float32 factor comes from the function mst_fx_gain uses on the host, compiled for the device. */
+int mst_fx_gain_items(const float *x_dev, float *y_dev, int n_items, long L, int C, const double *gain_db_dev, const int *invert_dev,
+                      const MstFxFuse *fuse, void *stream);
 /* AugmentationChain.apply_processor rms_normalize branch (:143-146): y *= sqrt(mean(x^2)/max(1e-7, mean(y^2)))
  * per item; per_x / per_y = samples per item of x and of y (L * channels each: the means are scalars over each array, and a
  * processor such as Panner / Haas may turn mono into stereo); scratch_dev: >= n_items*4 doubles */

@@ -48,6 +48,16 @@ class MstFxFuse(C.Structure):
 FX_COMP_SPLIT_SERIAL, FX_COMP_TIME_PARALLEL, FX_COMP_WAVE_SERIAL = 0, 1, 2      # MstFxCompressorPlan.form
 
 
+class MstFxBiquadItemsPlan(C.Structure):
+    """include/mst_hip.h MstFxBiquadItemsPlan (diagnostic; the layout may change with mst_version())."""
+    _fields_ = [("struct_size", C.c_uint), ("M", C.c_int), ("tables_offset", C.c_size_t), ("item_stride", C.c_size_t), ("powers_offset", C.c_size_t),
+                ("coef_offset", C.c_size_t), ("total_bytes", C.c_size_t)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = C.sizeof(MstFxBiquadItemsPlan)
+
+
 class MstFxBiquadPlan(C.Structure):
     """include/mst_hip.h MstFxBiquadPlan (diagnostic; the layout may change with mst_version())."""
     _fields_ = [("struct_size", C.c_uint), ("time_parallel", C.c_int), ("M", C.c_int), ("scan_threads", C.c_int), ("record_doubles", C.c_int),
@@ -131,6 +141,14 @@ SIGNATURES = {
     "mst_fx_biquad_tables": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "mst_fx_compressor_plan": (C.c_int, [C.c_int, C.c_long, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(MstFxCompressorPlan)]),
     "mst_fx_biquad_cascade": (C.c_int, [_F, _F, C.c_int, C.c_long, C.c_int, C.POINTER(C.c_double), C.c_int, _P, C.c_size_t, _P, _P]),
+    "mst_fx_biquad_items_scratch_bytes": (C.c_size_t, [C.c_int, C.c_long, C.c_int, C.c_int]),
+    "mst_fx_biquad_items_plan": (C.c_int, [C.c_int, C.c_long, C.c_int, C.c_int, C.POINTER(MstFxBiquadItemsPlan)]),
+    "mst_fx_biquad_cascade_items": (C.c_int, [_F, _F, C.c_int, C.c_long, C.c_int, _P, C.c_int, _P, C.c_size_t, _P, _P]),
+    "mst_fx_compressor_items_table_bytes": (C.c_size_t, [C.c_int]),
+    "mst_fx_compressor_items_prepare": (C.c_int, [_P, C.c_int, C.c_long, C.c_int, C.c_double, C.c_int, _P, C.c_size_t, C.POINTER(C.c_int)]),
+    "mst_fx_compressor_items": (C.c_int, [_F, _F, C.c_int, C.c_long, C.c_int, _P, _P, C.c_size_t, _P, _P]),
+    "mst_fx_midside_imager_items": (C.c_int, [_F, _F, C.c_int, C.c_long, _P, _P, _P, _P, _P]),
+    "mst_fx_gain_items": (C.c_int, [_F, _F, C.c_int, C.c_long, C.c_int, _P, _P, _P, _P]),
     "mst_fx_sumsq": (C.c_int, [_F, C.c_int, C.c_long, _P, _P]),
     "mst_fx_rms_pending": (C.c_int, [_P, _P, C.c_long, _P, C.c_long, _P, C.c_int, _P]),
     "mst_fx_scale_items": (C.c_int, [_F, _F, C.c_int, C.c_long, _P, _P]),

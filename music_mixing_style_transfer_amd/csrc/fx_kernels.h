@@ -92,8 +92,10 @@ struct BiquadChunkArgs {
     double *out_in_sumsq = nullptr;      // the apply pass also leaves sum(x_raw^2) here (the first rms-normalise of a chain needs it: no energy pass over x)
 };
 
+// (the body of a pass is a __device__ function of its argument block where that leaves the kernel's code as it was: the per-item kernels
+//  fxi_eq_* at the end of this file run the same function on one item's slice of the batch with that item's coefficients and table)
 template <bool APPLY, int NBANDS>
-__global__ __launch_bounds__(64) void fx_biquad_chunk_kernel(BiquadChunkArgs a) {
+__device__ __forceinline__ void fxb_biquad_chunk(const BiquadChunkArgs a) {
     const long gid = (long)blockIdx.x * 64 + threadIdx.x;
     if constexpr (!APPLY) {          // the state pass clears the energy slots the apply pass adds to (no memset launch in front of the call)
         if (a.out_sumsq)
@@ -180,6 +182,8 @@ __global__ __launch_bounds__(64) void fx_biquad_chunk_kernel(BiquadChunkArgs a) 
         if (a.out_in_sumsq) atomicAdd(&a.out_in_sumsq[item * MST_SUMSQ_SLOTS + (k & (MST_SUMSQ_SLOTS - 1))], ssx);
     }
 }
+template <bool APPLY, int NBANDS>
+__global__ __launch_bounds__(64) void fx_biquad_chunk_kernel(BiquadChunkArgs a) { fxb_biquad_chunk<APPLY, NBANDS>(a); }
 
 // Pass 1 without the recursion (round 5).  The zero-state end state of a chunk is LINEAR in its M input samples:
 //     e = sum_n h_(M-1-n) x[n],   h_m = A^m B = the cascade's state m steps after a unit impulse went in
@@ -189,7 +193,7 @@ __global__ __launch_bounds__(64) void fx_biquad_chunk_kernel(BiquadChunkArgs a) 
 // lane reads its row as broadcast ds_read_b128s.  Same sum as the recursion up to float64 rounding (the terms are added in time order, not
 // nested through the states).  The last chunk of a sequence, when it is short, has no successor: its end state is not needed (zeros).
 template <int NBANDS>
-__global__ __launch_bounds__(256) void fx_biquad_ends_kernel(BiquadChunkArgs a, const double *__restrict__ htab) {
+__device__ __forceinline__ void fxb_biquad_ends(const BiquadChunkArgs a, const double *__restrict__ htab) {
     // FOUR lanes per (sequence, chunk), a quarter of the chunk's samples each (M is a multiple of 16): 4 x the waves of one lane per chunk - at
     // 61 696 chunks one lane each is one wave per SIMD, whose load latency, LDS reads and multiply-adds then run one after the other (measured
     // 49 us like the recursion pass it replaced).  Lanes: quarter fastest (the four partial sums meet by two lane exchanges), then channel, chunk, item.
@@ -249,6 +253,8 @@ __global__ __launch_bounds__(256) void fx_biquad_ends_kernel(BiquadChunkArgs a, 
             *(double2 *)(a.ends + ((size_t)seq * a.nchunks + k) * (2 * MST_MAX_BANDS) + 2 * b) = full ? double2{acc[2 * b], acc[2 * b + 1]} : double2{0.0, 0.0};
     }
 }
+template <int NBANDS>
+__global__ __launch_bounds__(256) void fx_biquad_ends_kernel(BiquadChunkArgs a, const double *__restrict__ htab) { fxb_biquad_ends<NBANDS>(a, htab); }
 
 // ------------------------------------------------------------------------------------------------
 // STEREO chunks through LDS (round 5).  One lane per (channel, chunk) walks its chunk sample by sample; read straight from global memory
@@ -315,7 +321,7 @@ __device__ __forceinline__ void fx_stereo_to_lds(unsigned char *rows_lds, int la
 // pass 1 for stereo audio: fx_biquad_ends_kernel's dot products (e = sum_n h_(M-1-n) x[n]) on slabs.  A workgroup = four waves = 128
 // chunk pairs sharing the table segments (64 rows at a time).
 template <int NBANDS>
-__global__ __launch_bounds__(256) void fx_biquad_stereo_ends_kernel(BiquadChunkArgs a, const double *__restrict__ htab) {
+__device__ __forceinline__ void fxb_biquad_stereo_ends(const BiquadChunkArgs a, const double *__restrict__ htab) {
     constexpr int S = 2 * NBANDS, TT = 64;
     __shared__ __attribute__((aligned(16))) double tab[TT * S];
     __shared__ __attribute__((aligned(16))) unsigned char slab[4][32 * FXS_ROWB];
@@ -377,6 +383,8 @@ __global__ __launch_bounds__(256) void fx_biquad_stereo_ends_kernel(BiquadChunkA
             *(double2 *)(a.ends + ((size_t)seq * a.nchunks + k) * (2 * MST_MAX_BANDS) + 2 * b) = full ? double2{acc[2 * b], acc[2 * b + 1]} : double2{0.0, 0.0};
     }
 }
+template <int NBANDS>
+__global__ __launch_bounds__(256) void fx_biquad_stereo_ends_kernel(BiquadChunkArgs a, const double *__restrict__ htab) { fxb_biquad_stereo_ends<NBANDS>(a, htab); }
 
 // pass 1 for stereo audio on the float64 matrix cores (round 5).  fx_biquad_stereo_ends_kernel reads the impulse-state table from LDS - five
 // broadcast ds_read_b128 per sample and lane for ten multiply-adds: four waves keep the CU's LDS pipe busy ~2500 clocks per slab against 800
@@ -479,7 +487,7 @@ __global__ __launch_bounds__(256) void fx_biquad_stereo_ends_mfma_kernel(BiquadC
 // spilled scalar registers; this one runs ONE slab per loop trip behind a scheduling fence.)  Same recursion, same arithmetic per sample as
 // fx_biquad_chunk_kernel<true>: the same bits; the energy sums are added per chunk in the same order.
 template <int NBANDS>
-__global__ __launch_bounds__(256) void fx_biquad_stereo_apply_kernel(BiquadChunkArgs a) {
+__device__ __forceinline__ void fxb_biquad_stereo_apply(const BiquadChunkArgs a) {
     constexpr int D = 4;                               // slabs in flight
     __shared__ __attribute__((aligned(16))) unsigned char slab[4][32 * FXS_ROWB];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 1;
@@ -566,6 +574,8 @@ __global__ __launch_bounds__(256) void fx_biquad_stereo_apply_kernel(BiquadChunk
         if (a.out_in_sumsq) atomicAdd(&a.out_in_sumsq[item * MST_SUMSQ_SLOTS + (k & (MST_SUMSQ_SLOTS - 1))], ssx);
     }
 }
+template <int NBANDS>
+__global__ __launch_bounds__(256) void fx_biquad_stereo_apply_kernel(BiquadChunkArgs a) { fxb_biquad_stereo_apply<NBANDS>(a); }
 
 // s_0 = 0 ; s_k = A^M s_{k-1} + e_{k-1}: a first-order linear recurrence over the chunks with a matrix coefficient - scanned in
 // parallel.  One workgroup of NB = 256 or 512 threads per sequence; a block of NB - 1 chunks at a time: element 0 is the carry (the
@@ -1338,9 +1348,9 @@ __global__ __launch_bounds__(256) void fx_energy_parts_kernel(const float *x, do
 // tail folding (in_sumsq non-null): the rms-normalise behind the imager and a gain behind that, in this pass: s is the factor
 // fx_rms_pending_kernel computes (energy of the true input = sf^2 * sum of the raw input's slots), the store is (y * s) * post_gain
 // like fx_scale_kernel's x * sf * g
-__global__ __launch_bounds__(256) void fx_imager_apply_kernel(const float *x, float *y, const double *part, int chunks, long L,
-                                                              double bal_rounded, const double *in_scale, double *out_sumsq,
-                                                              const double *in_sumsq, float post_gain) {
+__device__ __forceinline__ void fxb_imager_apply(const float *x, float *y, const double *part, int chunks, long L,
+                                                 double bal_rounded, const double *in_scale, double *out_sumsq,
+                                                 const double *in_sumsq, float post_gain) {
     // a workgroup = MST_IMAGER_FRAMES frames of one item; its first wave adds the item's partial energies (and, when folding, the
     // slots of the input's energy) - one load per lane and the wave's butterfly sum, the order fx_rms_pending_kernel uses too
     __shared__ double sh[3];
@@ -1394,13 +1404,18 @@ __global__ __launch_bounds__(256) void fx_imager_apply_kernel(const float *x, fl
         }
     }
 }
+__global__ __launch_bounds__(256) void fx_imager_apply_kernel(const float *x, float *y, const double *part, int chunks, long L,
+                                                              double bal_rounded, const double *in_scale, double *out_sumsq,
+                                                              const double *in_sumsq, float post_gain) {
+    fxb_imager_apply(x, y, part, chunks, L, bal_rounded, in_scale, out_sumsq, in_sumsq, post_gain);
+}
 
 // Gain.process (:1041-1051) and the final multiply of the rms normalise (:145-146)
 // mode 0: y = g * x ; mode 1: y *= sqrt(ex / max(1e-7, ey)) with ex = acc_x/per_item, ey = acc_y/per_item
 // in_scale (chain fusion, mode 0): y = (x * (float)in_scale[item]) * g - the pending rms factor first, like the separate pass would
-__global__ __launch_bounds__(256) void fx_scale_kernel(const float *x, float *y, long per_item, float g,
-                                                       const double *acc_x, const double *acc_y, int mode, long per_x,
-                                                       const double *in_scale) {
+__device__ __forceinline__ void fxb_scale(const float *x, float *y, long per_item, float g,
+                                          const double *acc_x, const double *acc_y, int mode, long per_x,
+                                          const double *in_scale) {
     const int item = blockIdx.y;
     const float sf = in_scale ? (float)in_scale[item] : 1.0f;
     float scale = g;
@@ -1412,6 +1427,17 @@ __global__ __launch_bounds__(256) void fx_scale_kernel(const float *x, float *y,
     if (i >= per_item) return;
     const size_t off = (size_t)item * per_item + i;
     y[off] = (mode == 1 ? y[off] : x[off] * sf) * scale;
+}
+__global__ __launch_bounds__(256) void fx_scale_kernel(const float *x, float *y, long per_item, float g,
+                                                       const double *acc_x, const double *acc_y, int mode, long per_x,
+                                                       const double *in_scale) {
+    fxb_scale(x, y, per_item, g, acc_x, acc_y, mode, per_x, in_scale);
+}
+// Gain.process (:1041-1051): the float32 factor of a gain in dB (mst_fx_gain on the host, fxi_gain_kernel per item on the device)
+__host__ __device__ __forceinline__ float fx_gain_factor(double gain_db, int invert) {
+    double g = pow(10.0, gain_db / 20.0);
+    if (invert) g = -g;
+    return (float)g;
 }
 
 // Haas effect, haas_process (:768-786): y = x; y[:, ch] += feedback * np.roll(x[:, ch], delay).  np.roll is circular:
@@ -1795,4 +1821,635 @@ __global__ __launch_bounds__(256) void fx_sumsq_kernel(const float *x, double *o
     __syncthreads();
     if (threadIdx.x == 0) out[item * MST_SUMSQ_SLOTS + chunk] = (red[0] + red[1]) + (red[2] + red[3]);
     if (chunk == 0 && threadIdx.x >= chunks && threadIdx.x < MST_SUMSQ_SLOTS) out[item * MST_SUMSQ_SLOTS + threadIdx.x] = 0.0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Per-item parameters (mst_fx_*_items): item i of a batch runs with its own settings in the launches of the
+// shared-parameter call.  Every kernel below has the item on its grid's y axis (the scan: in its sequence index) and runs the BODY of the
+// shared kernel (the fxb_* functions above) on that item's slice of the batch - its audio, its chunk records, its energy slots, its
+// pending factor - with that item's coefficients and tables, which are uniform over the workgroup (scalar loads, like the kernel
+// arguments they stand in for).  Same function, same operands per (sequence, chunk): the bits of the shared call with those settings.
+// ------------------------------------------------------------------------------------------------
+// Item i's block of float64s at base + i * stride:
+//   [M][S] impulse states | [MST_BIQUAD_LEVELS][S][S] powers (A^M)^(2^l) | [MST_MAX_BANDS][5] b0 b1 b2 a1 a2 over a0
+// (S = 2 n_bands; the first two are biquad_host_tables' image, mst_fx.hip, without the A fragments: the per-item state pass of stereo audio is
+//  the VALU one, fx_biquad_stereo_ends_kernel's body - the same bits as the matrix-core pass, tests/fx_pass_ref.py check_forms_identical)
+struct FxiEqTabs {
+    double *base;
+    long stride, off_pow, off_coef;      // doubles
+    int M, n_bands;
+};
+
+// The builder: one workgroup per item, on the caller's stream in front of the state pass.  Thread S runs the cascade on a unit impulse
+// (the table), threads 0 .. S - 1 run it M steps on zero input from the unit states (the columns of A^M) - the recursions of
+// biquad_host_tables through fx_biquad_band; then the squarings (level by level in LDS, products and sums rounded separately like the
+// host's).  M * n_bands dependent steps per item: latency, not work.
+__global__ __launch_bounds__(64) void fxi_eq_tables_kernel(const double *__restrict__ coef6, FxiEqTabs t) {
+    __shared__ double pw[2][4 * MST_MAX_BANDS * MST_MAX_BANDS];          // the power level being squared and the one being made
+    const int item = blockIdx.x, tid = threadIdx.x, nb = t.n_bands, S = 2 * nb, M = t.M;
+    const double *c6 = coef6 + (size_t)item * nb * 6;
+    double *tab = t.base + (size_t)item * t.stride, *pm = tab + t.off_pow, *cfn = tab + t.off_coef;
+    if (tid <= S) {          // S column threads and the impulse thread: the only ones that need the coefficients
+        const bool impulse = tid == S;
+        double cf[MST_MAX_BANDS][5];
+#pragma unroll
+        for (int k = 0; k < MST_MAX_BANDS; ++k) {
+            const bool on = k < nb;
+            const double a0 = on ? c6[6 * k + 3] : 1.0;
+            cf[k][0] = on ? c6[6 * k + 0] / a0 : 0.0;
+            cf[k][1] = on ? c6[6 * k + 1] / a0 : 0.0;
+            cf[k][2] = on ? c6[6 * k + 2] / a0 : 0.0;
+            cf[k][3] = on ? c6[6 * k + 4] / a0 : 0.0;
+            cf[k][4] = on ? c6[6 * k + 5] / a0 : 0.0;
+            if (impulse) {
+#pragma unroll
+                for (int i = 0; i < 5; ++i) cfn[5 * k + i] = cf[k][i];
+            }
+        }
+        double z[2 * MST_MAX_BANDS];
+#pragma unroll
+        for (int j = 0; j < 2 * MST_MAX_BANDS; ++j) z[j] = (!impulse && j == tid) ? 1.0 : 0.0;
+        for (int m = 0; m < M; ++m) {
+            double v = (impulse && m == 0) ? 1.0 : 0.0;
+#pragma unroll
+            for (int k = 0; k < MST_MAX_BANDS; ++k)
+                if (k < nb) v = fx_biquad_band(v, z[2 * k], z[2 * k + 1], cf[k]);
+            if (impulse) {
+#pragma unroll
+                for (int j = 0; j < 2 * MST_MAX_BANDS; ++j)
+                    if (j < S) tab[(size_t)m * S + j] = z[j];
+            }
+        }
+        if (!impulse) {
+#pragma unroll
+            for (int j = 0; j < 2 * MST_MAX_BANDS; ++j)
+                if (j < S) {
+                    pm[j * S + tid] = z[j];
+                    pw[0][j * S + tid] = z[j];
+                }
+        }
+    }
+    __syncthreads();
+    for (int l = 1; l < MST_BIQUAD_LEVELS; ++l) {          // the levels stay in LDS; every level leaves for the table as it is made
+        const double *cur = pw[(l - 1) & 1];
+        double *nxt = pw[l & 1];
+        for (int e = tid; e < S * S; e += 64) {
+            const int r = e / S, c = e - r * S;
+            double acc = 0.0;
+            for (int j = 0; j < S; ++j) {
+                double p = cur[r * S + j] * cur[j * S + c];
+                MST_NO_CONTRACT(p);                      // the host squares with a rounded product and a rounded sum
+                acc += p;
+            }
+            nxt[e] = acc;
+            pm[(size_t)l * S * S + e] = acc;
+        }
+        __syncthreads();
+    }
+}
+
+// the argument block of one item: the shared call's, cut to the item's slice, with the item's coefficients
+__device__ __forceinline__ BiquadChunkArgs fxi_eq_slice(const BiquadChunkArgs &a, const FxiEqTabs &t, int item) {
+    BiquadChunkArgs b = a;
+    const size_t per = (size_t)a.L * a.C, rec = (size_t)item * a.C * a.nchunks * (2 * MST_MAX_BANDS);
+    b.x = a.x + item * per;
+    b.y = a.y + item * per;
+    b.ends = a.ends + rec;
+    b.starts = a.starts + rec;
+    b.n_seq = a.C;
+    b.in_scale = a.in_scale ? a.in_scale + item : nullptr;
+    b.out_sumsq = a.out_sumsq ? a.out_sumsq + (size_t)item * MST_SUMSQ_SLOTS : nullptr;
+    b.out_in_sumsq = a.out_in_sumsq ? a.out_in_sumsq + (size_t)item * MST_SUMSQ_SLOTS : nullptr;
+    const double *cf = t.base + (size_t)item * t.stride + t.off_coef;
+#pragma unroll
+    for (int k = 0; k < MST_MAX_BANDS; ++k)
+#pragma unroll
+        for (int i = 0; i < 5; ++i) b.coef[k][i] = cf[5 * k + i];
+    return b;
+}
+template <int NBANDS>
+__global__ __launch_bounds__(256) void fxi_eq_ends_kernel(BiquadChunkArgs a, FxiEqTabs t) {
+    fxb_biquad_ends<NBANDS>(fxi_eq_slice(a, t, blockIdx.y), t.base + (size_t)blockIdx.y * t.stride);
+}
+template <int NBANDS>
+__global__ __launch_bounds__(256) void fxi_eq_stereo_ends_kernel(BiquadChunkArgs a, FxiEqTabs t) {
+    fxb_biquad_stereo_ends<NBANDS>(fxi_eq_slice(a, t, blockIdx.y), t.base + (size_t)blockIdx.y * t.stride);
+}
+// fx_biquad_scan_kernel with the powers of the sequence's item: one workgroup per sequence, the same Hillis-Steele scan, the same
+// multiply-adds in the same order (as a function shared by both kernels it changed the shared kernel's register allocation, so the shared
+// kernel stays as it is and this one repeats its steps; tests/test_fx_items_*.py hold the two to the same bits)
+template <int NBANDS, int NB>
+// (ends / starts are __restrict__: the powers, reached through the table pointer, are then known not to be written by this kernel and
+//  stay uniform scalar loads like the shared kernel's __restrict__ argument)
+__global__ __launch_bounds__(NB) void fxi_eq_scan_kernel(const double *__restrict__ ends, double *__restrict__ starts, FxiEqTabs tb, int C, int nchunks) {
+    constexpr int SM = 2 * MST_MAX_BANDS, S = 2 * NBANDS, NL = NB == 512 ? 9 : 8;
+    static_assert(NB == 256 || NB == 512, "elements per block");
+    __shared__ double st[2][S][NB];
+    const int seq = blockIdx.x, i = threadIdx.x;
+    const double *__restrict__ pm = tb.base + (size_t)(seq / C) * tb.stride + tb.off_pow;      // uniform: scalar loads
+    double carry[S];
+#pragma unroll
+    for (int j = 0; j < S; ++j) carry[j] = 0.0;
+    for (int k0 = 0; k0 < nchunks; k0 += NB - 1) {
+        double t[S];
+        const int kc = k0 + i - 1;
+        const bool have = i > 0 && kc < nchunks;
+        const double2 *rec = (const double2 *)(ends + ((size_t)seq * nchunks + (have ? kc : 0)) * SM);
+#pragma unroll
+        for (int j = 0; j < S; j += 2) {
+            const double2 v = rec[j / 2];
+            t[j] = v.x;
+            t[j + 1] = v.y;
+        }
+#pragma unroll
+        for (int j = 0; j < S; ++j) {
+            t[j] = i == 0 ? carry[j] : (have ? t[j] : 0.0);
+            st[0][j][i] = t[j];
+        }
+        __syncthreads();
+        int cur = 0;
+#pragma unroll
+        for (int l = 0; l < NL; ++l) {
+            const int d = 1 << l;
+            if (i >= d) {
+                double u[S];
+#pragma unroll
+                for (int j = 0; j < S; ++j) u[j] = st[cur][j][i - d];
+#pragma unroll
+                for (int r = 0; r < S; ++r) {
+                    double acc = t[r];
+#pragma unroll
+                    for (int j = 0; j < S; ++j) acc = fma(pm[(l * S + r) * S + j], u[j], acc);
+                    t[r] = acc;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < S; ++j) st[cur ^ 1][j][i] = t[j];
+            __syncthreads();
+            cur ^= 1;
+        }
+        if (i < NB - 1 && k0 + i < nchunks) {
+            double2 *out = (double2 *)(starts + ((size_t)seq * nchunks + k0 + i) * SM);
+#pragma unroll
+            for (int j = 0; j < S; j += 2) out[j / 2] = double2{t[j], t[j + 1]};
+        }
+#pragma unroll
+        for (int j = 0; j < S; ++j) carry[j] = st[cur][j][NB - 1];
+        __syncthreads();
+    }
+}
+template <int NBANDS>
+__global__ __launch_bounds__(64) void fxi_eq_chunk_apply_kernel(BiquadChunkArgs a, FxiEqTabs t) {
+    fxb_biquad_chunk<true, NBANDS>(fxi_eq_slice(a, t, blockIdx.y));
+}
+template <int NBANDS>
+__global__ __launch_bounds__(256) void fxi_eq_stereo_apply_kernel(BiquadChunkArgs a, FxiEqTabs t) {
+    fxb_biquad_stereo_apply<NBANDS>(fxi_eq_slice(a, t, blockIdx.y));
+}
+// the serial form (no scratch, or a single chunk): one lane per (item, channel) sequence like fx_biquad_kernel, its steps through
+// fx_biquad_band with the coefficients straight from the caller's [n_items][n_bands][6].  grid ceil(n_seq / 64)
+__global__ __launch_bounds__(64) void fxi_eq_serial_kernel(BiquadArgs a, const double *__restrict__ coef6) {
+    const int seq = blockIdx.x * 64 + threadIdx.x;
+    if (seq >= a.n_seq) return;
+    const int item = seq / a.C, c = seq % a.C;
+    const double *c6 = coef6 + (size_t)item * a.n_bands * 6;
+    double cf[MST_MAX_BANDS][5];
+#pragma unroll
+    for (int k = 0; k < MST_MAX_BANDS; ++k) {
+        const bool on = k < a.n_bands;
+        const double a0 = on ? c6[6 * k + 3] : 1.0;
+        cf[k][0] = on ? c6[6 * k + 0] / a0 : 0.0;
+        cf[k][1] = on ? c6[6 * k + 1] / a0 : 0.0;
+        cf[k][2] = on ? c6[6 * k + 2] / a0 : 0.0;
+        cf[k][3] = on ? c6[6 * k + 4] / a0 : 0.0;
+        cf[k][4] = on ? c6[6 * k + 5] / a0 : 0.0;
+    }
+    const float *xp = a.x + (size_t)item * a.L * a.C + c;
+    float *yp = a.y + (size_t)item * a.L * a.C + c;
+    double z1[MST_MAX_BANDS], z2[MST_MAX_BANDS];
+#pragma unroll
+    for (int k = 0; k < MST_MAX_BANDS; ++k) z1[k] = z2[k] = 0.0;
+    for (long n = 0; n < a.L; ++n) {
+        double v = (double)xp[n * a.C];
+#pragma unroll
+        for (int k = 0; k < MST_MAX_BANDS; ++k)
+            if (k < a.n_bands) v = fx_biquad_band(v, z1[k], z2[k], cf[k]);
+        yp[n * a.C] = (float)v;
+    }
+}
+
+// MidSideImager and Gain per item: fx_imager_apply_kernel / fx_scale_kernel already have the item on the grid's y axis
+__global__ __launch_bounds__(256) void fxi_imager_apply_kernel(const float *x, float *y, const double *part, int chunks, long L,
+                                                               const double *__restrict__ bal, const double *in_scale, double *out_sumsq,
+                                                               const double *in_sumsq, const float *__restrict__ post_gain_items, float post_gain) {
+    const int item = blockIdx.y;
+    const double bal_r = round(bal[item] * 1000.0) / 1000.0;      // round(bal, 3) like mst_fx_midside_imager
+    fxb_imager_apply(x, y, part, chunks, L, bal_r, in_scale, out_sumsq, in_sumsq, post_gain_items ? post_gain_items[item] : post_gain);
+}
+__global__ __launch_bounds__(256) void fxi_gain_kernel(const float *x, float *y, long per_item, const double *__restrict__ gain_db,
+                                                       const int *__restrict__ invert, const double *in_scale) {
+    const int item = blockIdx.y;
+    fxb_scale(x, y, per_item, fx_gain_factor(gain_db[item], invert ? invert[item] : 0), nullptr, nullptr, 0, per_item, in_scale);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The compressor per item (mst_fx_compressor_items).  Threshold and ratio per item travel as CompArgs::thr_items / ratio_items like the
+// parameter grid's (fx_comp_curve); the attack / release coefficients and the slopes of the chunk maps' pieces come from the table
+// mst_fx_compressor_items_prepare filled on the host with the shared call's own functions.  fx_comp_gain_kernel and
+// fx_comp_apply_kernel<false> serve the split-serial form as they are (they never see a time constant).  The kernels below are
+// fx_compressor_kernel, fx_comp_smooth_kernel, fx_comp_map_kernel, fx_comp_chain_kernel and fx_comp_apply_kernel<true> step for step with
+// those values read per sequence (a chain workgroup serves one sequence: its item's slope rows are loaded once) - the shared kernels keep
+// their code and their registers, the arithmetic per sample goes through the same fx_comp_curve / fx_comp_level_diff / fx_log10_f32, and
+// tests/test_fx_items_*.py hold item i to the bits of the shared call with item i's settings.
+// ------------------------------------------------------------------------------------------------
+struct FxiCmpTab {
+    const double *aA, *aR;        // [n_items] attack / release coefficients
+    const double *slope, *inv;    // [n_items][2][MST_COMP_NP]: CompMapArgs::slope / inv_slope of the item
+    int C;
+};
+__global__ __launch_bounds__(256) void fxi_cmp_serial_kernel(CompArgs a, FxiCmpTab tb) {
+    const int lane = threadIdx.x & 63;
+    const int seq = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (seq >= a.n_seq) return;   // wave-uniform
+    const int item = seq / a.C, c = seq % a.C;
+    const double thr = a.thr_items[item], ratio = a.ratio_items[item], aatt = tb.aA[item], arel = tb.aR[item];
+    const float *xp = a.x + (size_t)item * a.L * a.C + c;
+    float *yp = a.y + (size_t)item * a.L * a.C + c;
+    double prev = 0.0;            // yL_prev is forced to 0 on entry (:553)
+    for (long n0 = 0; n0 < a.L; n0 += 64) {
+        const long n = n0 + lane;
+        const double xv = (n < a.L) ? (double)xp[n * a.C] : 0.0;
+        const double ax = fabs(xv);
+        const double xg = (ax < 0.000001) ? -120.0 : 20.0 * log10(ax);
+        double yg = 0.0;          // ratio == 1: neither branch assigns y_g (:564-573)
+        if (ratio > 1.0)
+            yg = (xg >= thr) ? thr + (xg - thr) / ratio : xg;
+        else if (ratio < 1.0)
+            yg = (xg <= thr) ? thr + (xg - thr) / (1.0 / ratio) : xg;
+        const double xl = xg - yg;
+        double yl = 0.0;
+        const int cnt = (a.L - n0) < 64 ? (int)(a.L - n0) : 64;
+        for (int i = 0; i < cnt; ++i) {
+            const double v = __shfl(xl, i);
+            if (v > prev)
+                prev = aatt * prev + (1.0 - aatt) * v;
+            else
+                prev = arel * prev + (1.0 - arel) * v;
+            if (lane == i) yl = prev;
+        }
+        if (n < a.L) yp[n * a.C] = (float)(xv * pow(10.0, (a.makeup - yl) / 20.0));
+    }
+}
+
+__global__ __launch_bounds__(64) void fxi_cmp_smooth_kernel(CompArgs a, double *xl, FxiCmpTab tb) {
+    const int seq = blockIdx.x * 64 + threadIdx.x;
+    const bool live = seq < a.n_seq;
+    // y <- alpha y + (1 - alpha) x, alpha = attack coefficient when x > y else release, evaluated as y + c (x - y) with
+    // c = 1 - alpha picked by the sign of d = x - y: three float64 operations per step (add, compare, fma) instead of five plus
+    // 64-bit address arithmetic.  A float64 VALU op issues in 8 clocks on gfx950 and the steps are one dependent chain:
+    // measured 140 clocks per step with per-lane cache lines, 99 with the time-major layout and the two-product form, 85 with
+    // this one (computing both candidates and selecting afterwards is not faster: 88).  Same value up to float64 rounding.
+    // Addresses are a uniform base + a 32-bit byte offset (scratch < 4 GiB is checked by the host).
+    unsigned char *base = (unsigned char *)xl;
+    const unsigned row = (unsigned)a.n_seq * 8u;                       // bytes per time step
+    const unsigned off0 = (unsigned)(live ? seq : a.n_seq - 1) * 8u;   // idle lanes of the last wave shadow a live one, store nothing
+    const int item = (live ? seq : a.n_seq - 1) / a.C;
+    const double ca = 1.0 - tb.aA[item], cr = 1.0 - tb.aR[item];
+    double prev = 0.0;
+    constexpr int NB = 16;
+    const long nfull = a.L / NB;
+    double nx[NB];
+    if (nfull > 0) {
+#pragma unroll
+        for (int i = 0; i < NB; ++i) nx[i] = *(const double *)(base + (size_t)(off0 + (unsigned)i * row));
+    }
+    for (long bt = 0; bt < nfull; ++bt) {
+        double v[NB];
+#pragma unroll
+        for (int i = 0; i < NB; ++i) v[i] = nx[i];
+        const unsigned nn = (unsigned)((bt + 1 < nfull) ? (bt + 1) * NB : bt * NB);      // last batch: harmless reload
+#pragma unroll
+        for (int i = 0; i < NB; ++i) nx[i] = *(const double *)(base + (size_t)(off0 + (nn + (unsigned)i) * row));
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const double d = v[i] - prev;
+            prev = fma(d > 0.0 ? ca : cr, d, prev);
+            v[i] = prev;
+        }
+        if (live) {
+#pragma unroll
+            for (int i = 0; i < NB; ++i) *(double *)(base + (size_t)(off0 + ((unsigned)(bt * NB) + (unsigned)i) * row)) = v[i];
+        }
+    }
+    for (long n = nfull * NB; n < a.L; ++n) {
+        double *q = (double *)(base + (size_t)(off0 + (unsigned)n * row));
+        const double d = *q - prev;
+        prev = fma(d > 0.0 ? ca : cr, d, prev);
+        if (live) *q = prev;
+    }
+}
+
+// (convex and concave items share a wave: the branch of the piece update is a select per lane)
+__global__ __launch_bounds__(64) MST_HEAVY_UNROLL void fxi_cmp_map_kernel(CompMapArgs a, CompArgs ca, FxiCmpTab tb) {
+    constexpr int PASS = 16;                                        // doubles of every record that cross the LDS tile at a time (128 B)
+    __shared__ double tr[64 * (PASS + 1)];
+    __shared__ double tab[256];
+    const int k = blockIdx.x + a.chunk0;
+    const int seq = blockIdx.y * 64 + threadIdx.x;
+    const bool live = seq < a.n_seq;
+    const size_t sq = live ? seq : a.n_seq - 1;
+    // the level differences x_l are computed here from the audio (a lane walks its own sequence: 32 frames = 256 contiguous bytes that
+    // it shares with the lane of the other channel), not read from a float64 scratch that a separate pass would have to write
+    for (int i = threadIdx.x; i < 256; i += 64) tab[i] = a.log_tab[i];
+    const int item = (int)(sq / ca.C);
+    const FxCompCurve cv = fx_comp_curve(ca, item);
+    const double aA = tb.aA[item], aR = tb.aR[item], cA = 1.0 - aA, cR = 1.0 - aR;
+    const bool use_min = aA > aR;
+    const float *xp = ca.x + ((size_t)(ca.shared_x ? 0 : item) * ca.L) * ca.C + sq % ca.C;
+    __builtin_amdgcn_wave_barrier();
+    double lb[MST_COMP_NP + 1];                                     // lb[1 .. t]: the values at which the pieces meet after t steps
+    double b0 = 0.0;                                                // the lowest piece (always the attack branch); identity before step 1
+#pragma unroll
+    for (int t = 0; t < MST_COMP_T; ++t) {
+        const long n = (long)k * MST_COMP_T + t;
+        if (n < a.L) {                                              // uniform over the wave
+            const double x = fx_comp_level_diff(xp[(size_t)n * ca.C] * cv.sf, cv.thr, cv.mul, cv.mode, tab);
+            const double oA = cA * x, oR = cR * x;
+            b0 = fma(aA, b0, oA);
+            // downwards, in place: slot s reads the old slots s and s - 1.  g = f_x(old value) = max (convex) / min (concave) of the branches
+            double m = x;                                           // min(g_s, x); above the top piece: x
+#pragma unroll
+            for (int s = t + 1; s >= 1; --s) {
+                if (s > 1) {
+                    const double v = lb[s - 1];
+                    const double gA = fma(aA, v, oA), gR = fma(aR, v, oR);
+                    const double g = use_min ? fmin(gA, gR) : fmax(gA, gR);
+                    lb[s] = fmax(g, m);
+                    m = fmin(g, x);
+                } else {
+                    lb[1] = m;
+                }
+            }
+        }
+    }
+    const long left = a.L - (long)k * MST_COMP_T;
+    const int nsteps = left < MST_COMP_T ? (int)left : MST_COMP_T;  // uniform; >= 1
+    // the record (b_0, lb_1 .. lb_T, pad) leaves in passes of 16 doubles through a [lane][16 + 1] tile: every store instruction of the
+    // wave writes 128 contiguous bytes of four records
+    const int nlive = a.n_seq - blockIdx.y * 64 < 64 ? a.n_seq - blockIdx.y * 64 : 64;
+    double *row = tr + threadIdx.x * (PASS + 1);
+    double *mbase = a.maps + ((size_t)(blockIdx.y * 64) * a.nchunks + k) * MST_COMP_REC;
+    auto pass = [&](auto J) {                                       // two flat loops: both unroll early, lb stays in registers
+        constexpr int p0 = decltype(J)::value * PASS, p1 = p0 + PASS < MST_COMP_REC ? p0 + PASS : MST_COMP_REC;
+        constexpr int cnt = p1 - p0;                                // doubles in this pass
+#pragma unroll
+        for (int p = p0; p < p1; ++p) row[p - p0] = p == 0 ? b0 : ((p <= nsteps && p <= MST_COMP_T) ? lb[p <= MST_COMP_T ? p : 0] : MST_COMP_NEVER);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int i = 0; i < cnt; ++i) {                             // 64 records x cnt doubles, lane-linear over (record, double)
+            const int idx = i * 64 + threadIdx.x, r = idx / cnt, c = idx % cnt;
+            if (r < nlive) mbase[(size_t)r * a.nchunks * MST_COMP_REC + p0 + c] = tr[r * (PASS + 1) + c];
+        }
+        __builtin_amdgcn_wave_barrier();
+    };
+    static_assert(MST_COMP_REC <= 3 * PASS, "three passes cover the record");
+    pass(std::integral_constant<int, 0>{});
+    pass(std::integral_constant<int, 1>{});
+    pass(std::integral_constant<int, 2>{});
+}
+
+__global__ __launch_bounds__(MST_CHAIN_THREADS) void fxi_cmp_chain_kernel(CompMapArgs a, FxiCmpTab tb) {
+    constexpr int CB = MST_CHAIN_CB, REC = MST_COMP_REC, NPE = MST_COMP_NP + 1, ENT = 2 * NPE;      // chunks per batch, doubles per record / per chunk of entries
+    constexpr int NH = MST_CHAIN_HELPERS, HB = CB / NH;               // helper waves; chunks per helper wave and batch
+    constexpr int NLD = (HB * REC / 2 + 63) / 64;                     // 16-byte loads per helper lane per batch
+    static_assert(REC % 2 == 0 && HB % 2 == 0, "records are whole 16-byte units; a helper takes its chunks two at a time");
+    __shared__ __attribute__((aligned(16))) double raw[NH][HB * REC];
+    __shared__ __attribute__((aligned(16))) double cooked[2][CB * ENT];      // per (chunk, piece): b, u; entry NP is never selected
+    static_assert(NH == 4, "helper waves 1, 2, 3, 5");
+    const int seq = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hw = wave == 5 ? 3 : (wave > 0 ? wave - 1 : 0);
+    const bool helper = wave != 0 && wave != 4;
+    const double *sl0 = tb.slope + (size_t)(seq / tb.C) * 2 * MST_COMP_NP, *sl1 = sl0 + MST_COMP_NP;      // the item of this sequence: its rows, once
+    const double *is0 = tb.inv + (size_t)(seq / tb.C) * 2 * MST_COMP_NP, *is1 = is0 + MST_COMP_NP;
+    const double2 *m = (const double2 *)(a.maps + (size_t)seq * a.nchunks * REC);
+    const size_t total = (size_t)a.nchunks * REC / 2;
+    const int nbatch = a.batch1;                                      // this launch walks batches batch0 .. batch1 - 1
+    // ---- waves 1, 2: global -> registers -> raw records in LDS -> entries
+    const int hp = (lane & 31) + 1;                                   // the piece this helper lane rebuilds (1 .. T)
+    const double sl_full = sl0[hp], isl_full = is0[hp - 1], sl_last = sl1[hp], isl_last = is1[hp - 1];
+    double rx[NLD], ry[NLD];                                          // (plain doubles: an array of double2 stays in scratch memory)
+    auto load = [&](int bt) {
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const size_t e = ((size_t)(bt < nbatch ? bt : nbatch - 1) * CB + hw * HB) * (REC / 2) + (size_t)i * 64 + lane;
+            const double2 v = m[e < total ? e : total - 1];
+            rx[i] = v.x;
+            ry[i] = v.y;
+        }
+    };
+    // the records of batch bt leave the registers for LDS, the loads of batch bt + 1 are issued at once (a whole batch of walking and
+    // rebuilding covers their latency), then the entries of batch bt are rebuilt
+    auto cook = [&](int buf, int bt) {
+        double2 *dst = (double2 *)raw[hw];
+#pragma unroll
+        for (int i = 0; i < NLD; ++i)
+            if (i * 64 + lane < HB * REC / 2) dst[i * 64 + lane] = double2{rx[i], ry[i]};
+        load(bt + 1);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int it = 0; it < HB / 2; ++it) {
+            const int c = 2 * it + (lane >> 5);                       // chunk of this half-wave within the helper's share
+            const double *rec = raw[hw] + c * REC;
+            const double lbp = rec[hp], lbm = rec[hp - 1];            // rec[0] = b_0
+            const bool valid = lbp < 0.5 * MST_COMP_NEVER;            // the piece exists (the last chunk may be short)
+            const bool shortc = (long)(bt * CB + hw * HB + c + 1) * MST_COMP_T > a.L;
+            const double d = valid ? (lbp - lbm) * (shortc ? isl_last : isl_full) : 0.0;
+            const double u = mst_half_prefix_sum_f64(d);
+            double *q = cooked[buf] + ((hw * HB + c) * NPE + hp) * 2;
+            q[0] = valid ? fma(-(shortc ? sl_last : sl_full), u, lbp) : 0.0;
+            q[1] = valid ? u : MST_COMP_NEVER;
+            if (hp == 1) {                                            // the lowest piece: reached by every y
+                q[-2] = lbm;
+                q[-1] = -MST_COMP_NEVER;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    };
+    if (helper) {
+        for (int i = lane; i < 2 * HB; i += 64) {                     // the entry the lanes without a piece read: written once
+            double *q = &cooked[i / HB][((hw * HB + i % HB) * NPE + MST_COMP_NP) * 2];
+            q[0] = 0.0;
+            q[1] = MST_COMP_NEVER;
+        }
+        load(a.batch0);
+        cook(0, a.batch0);
+    }
+    __syncthreads();
+    // yL_prev = 0 on entry (common_audioeffects.py:553); a later time slice continues from the value the slice before it left
+    MstUniformF64 yu = mst_wave_read_u64(a.batch0 > 0 ? a.ycarry[seq] : 0.0, 0);
+    const int pl = lane < MST_COMP_NP ? MST_COMP_NP - 1 - lane : MST_COMP_NP;   // descending; lanes without a piece read the "never" entry
+    const double a_full = pl < MST_COMP_NP ? sl0[pl] : 0.0, a_last = pl < MST_COMP_NP ? sl1[pl] : 0.0;
+    for (int bt = a.batch0; bt < nbatch; ++bt) {
+        const int cur = (bt - a.batch0) & 1;
+        if (helper) {
+            if (bt + 1 < nbatch) {
+                cook(cur ^ 1, bt + 1);
+            }
+        } else if (wave == 0) {
+            const int nc = a.nchunks - bt * CB < CB ? a.nchunks - bt * CB : CB;
+            struct Piece { double pb, u; };
+            const double *base = cooked[cur] + 2 * pl;
+            auto fetch = [&](int c) {
+                const double2 q = *(const double2 *)(base + ENT * (c < CB ? c : CB - 1));
+                return Piece{q.x, q.y};
+            };
+            double keep = 0.0;                                      // lane c holds the start value of chunk c
+            if ((long)(bt + 1) * CB * MST_COMP_T <= a.L) {          // a whole batch of whole chunks: 32 steps in one basic block, y stays in SGPRs
+                Piece p[4];
+                p[0] = fetch(0); p[1] = fetch(1); p[2] = fetch(2);
+                yu = mst_wave_uniform(yu);
+#define MST_CHAIN_STEP(c)                                                                                              \
+    {                                                                                                                  \
+        p[((c) + 3) & 3] = fetch((c) + 3);                                                                             \
+        keep = mst_wave_park_f64<(c)>(keep, yu);                                                                       \
+        const Piece &q = p[(c) & 3];                                                                                   \
+        yu = mst_wave_first_ge(yu, q.u, fma(a_full, yu.value(), q.pb));                                                \
+    }
+#define MST_CHAIN_STEP8(c) MST_CHAIN_STEP(c) MST_CHAIN_STEP((c) + 1) MST_CHAIN_STEP((c) + 2) MST_CHAIN_STEP((c) + 3) \
+    MST_CHAIN_STEP((c) + 4) MST_CHAIN_STEP((c) + 5) MST_CHAIN_STEP((c) + 6) MST_CHAIN_STEP((c) + 7)
+                static_assert(CB == 32, "four groups of eight steps");
+                MST_CHAIN_STEP8(0) MST_CHAIN_STEP8(8) MST_CHAIN_STEP8(16) MST_CHAIN_STEP8(24)
+#undef MST_CHAIN_STEP8
+#undef MST_CHAIN_STEP
+            } else {                                                // the last batch: ragged, or its last chunk is short
+                for (int c = 0; c < nc; ++c) {
+                    const Piece q = fetch(c);
+                    const double y = yu.value();
+                    keep = lane == c ? y : keep;
+                    const double sa = (long)(bt * CB + c + 1) * MST_COMP_T > a.L ? a_last : a_full;
+                    yu = mst_wave_first_ge(yu, q.u, fma(sa, y, q.pb));
+                }
+            }
+            if (lane < nc) a.ystart[(size_t)(bt * CB + lane) * a.n_seq + seq] = keep;
+            if (bt + 1 == nbatch && lane == 0) a.ycarry[seq] = yu.value();
+        }
+        __syncthreads();
+    }
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(256) void fxi_cmp_apply_kernel(CompArgs a, const double *yl, const double *ystart, int nchunks, int tile0, double *tile_sums, FxiCmpTab tb) {
+    __shared__ double t[64][65];
+    const long tx = (long)blockIdx.x + tile0;                       // time tile (a launch covers the tiles of one time slice)
+    const long n0 = tx * 64;
+    const int s0 = blockIdx.y * 64;
+    float xv[16];
+    if constexpr (FILL) {
+        static_assert(MST_COMP_T == 32, "two chunks per 64-step tile");
+        // yl = the log10 table: the level differences are recomputed from the audio (audio side: lanes along time), the smoother runs
+        // along time in LDS (sequence side), the result stays in the tile for the gain application below
+        __shared__ double tab[256];
+        __shared__ double sthr[64], smul[64];
+        __shared__ int smode[64];
+        __shared__ float ssf[64];
+        tab[threadIdx.x] = yl[threadIdx.x];
+        if (threadIdx.x < 64) {
+            const int seq = s0 + threadIdx.x < a.n_seq ? s0 + threadIdx.x : a.n_seq - 1;
+            const FxCompCurve c = fx_comp_curve(a, seq / a.C);
+            sthr[threadIdx.x] = c.thr; smul[threadIdx.x] = c.mul; smode[threadIdx.x] = c.mode; ssf[threadIdx.x] = c.sf;
+        }
+        // this thread's 16 samples (scaled), all loads in flight before the first use; kept in registers for the gain application
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const int idx = k * 256 + threadIdx.x, sq = s0 + (idx >> 6);
+            const long n = n0 + (idx & 63);
+            const bool ok = sq < a.n_seq && n < a.L;
+            const int sc = ok ? sq : 0;
+            xv[k] = a.x[((size_t)(a.shared_x ? 0 : sc / a.C) * a.L + (ok ? n : 0)) * a.C + sc % a.C];      // never a predicated load
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {                               // (full unroll: xv stays in registers)
+            const int idx = k * 256 + threadIdx.x, sl = idx >> 6, nl = idx & 63;
+            xv[k] *= ssf[sl];
+            t[nl][sl] = (s0 + sl < a.n_seq && n0 + nl < a.L) ? fx_comp_level_diff(xv[k], sthr[sl], smul[sl], smode[sl], tab) : 0.0;
+        }
+        __syncthreads();
+        const int sl = threadIdx.x & 63, hh = threadIdx.x >> 6;
+        const long k = tx * 2 + hh;
+        if (hh < 2 && s0 + sl < a.n_seq && k < nchunks) {
+            const double cA = 1.0 - tb.aA[(s0 + sl) / a.C], cR = 1.0 - tb.aR[(s0 + sl) / a.C];
+            double prev = ystart[(size_t)k * a.n_seq + s0 + sl];
+#pragma unroll
+            for (int i = 0; i < MST_COMP_T; ++i) {
+                const double d = t[hh * MST_COMP_T + i][sl] - prev;
+                prev = fma(d > 0.0 ? cA : cR, d, prev);
+                t[hh * MST_COMP_T + i][sl] = prev;
+            }
+        }
+    } else {
+#pragma unroll 4
+        for (int k = 0; k < 16; ++k) {
+            const int idx = k * 256 + threadIdx.x, nl = idx >> 6, sl = idx & 63;
+            t[nl][sl] = (s0 + sl < a.n_seq && n0 + nl < a.L) ? yl[(size_t)(n0 + nl) * a.n_seq + s0 + sl] : 0.0;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int idx = k * 256 + threadIdx.x, sl = idx >> 6, nl = idx & 63;
+        const int seq = s0 + sl;
+        const long n = n0 + nl;
+        if (seq < a.n_seq && n < a.L) {
+            const size_t e = ((size_t)(seq / a.C) * a.L + n) * a.C + seq % a.C;
+            const size_t ex = a.shared_x ? (size_t)n * a.C + seq % a.C : e;
+            const float xs = FILL ? xv[k] : a.x[ex] * (a.in_scale ? (float)a.in_scale[seq / a.C] : 1.0f);
+            // 10^(v / 20) as exp(v ln10 / 20): the general pow() is five times the instructions for the same value to 1e-15 relative
+            const float out = (float)((double)xs * exp((a.makeup - t[nl][sl]) * 0.11512925464970228420));
+            a.y[e] = out;
+            if (a.out_sumsq) t[nl][sl] = a.out_ms ? (double)out : (double)out * (double)out;      // this thread's own tile element: reused for the energy sums
+        } else if (a.out_sumsq) {
+            t[nl][sl] = 0.0;
+        }
+    }
+    if (a.out_sumsq && a.out_ms) {
+        // stereo chain, an imager downstream: the tile holds the OUTPUT samples (exact float32 values); thread (pair p = tid & 31, frames
+        // nl = 8 (tid >> 5) .. + 7) forms l^2 + r^2 and the imager's mid / side terms - m = l + r, s = l - r and their squares in float32,
+        // sums in float64, like fx_energy_parts_kernel - then lanes p and p + 32 meet by a shuffle, the four waves through LDS, and pair p
+        // writes the tile's three partial sums of its item (C == 2: the tile's sequences 2 p, 2 p + 1 are the channels of one item)
+        __shared__ double red[4][32][3];
+        __syncthreads();
+        const int p = threadIdx.x & 31, g8 = threadIdx.x >> 5;
+        double e2 = 0.0, em = 0.0, es = 0.0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float l = (float)t[8 * g8 + i][2 * p], r = (float)t[8 * g8 + i][2 * p + 1];
+            const float m = l + r, sd = l - r;
+            e2 += (double)l * (double)l + (double)r * (double)r;
+            em += (double)(m * m);
+            es += (double)(sd * sd);
+        }
+        e2 += __shfl_xor(e2, 32);
+        em += __shfl_xor(em, 32);
+        es += __shfl_xor(es, 32);
+        if ((threadIdx.x & 63) < 32) {
+            red[threadIdx.x >> 6][p][0] = e2;
+            red[threadIdx.x >> 6][p][1] = em;
+            red[threadIdx.x >> 6][p][2] = es;
+        }
+        __syncthreads();
+        if (threadIdx.x < 32 && s0 + 2 * p < a.n_seq) {
+            double *q = tile_sums + ((size_t)tx * (a.n_seq / 2) + (s0 + 2 * p) / 2) * 3;
+            q[0] = (red[0][p][0] + red[1][p][0]) + (red[2][p][0] + red[3][p][0]);
+            q[1] = (red[0][p][1] + red[1][p][1]) + (red[2][p][1] + red[3][p][1]);
+            q[2] = (red[0][p][2] + red[1][p][2]) + (red[2][p][2] + red[3][p][2]);
+        }
+    } else if (a.out_sumsq) {             // column sums of the tile: one partial per (tile, sequence); the reduction adds the channels of an item
+        __syncthreads();
+        if (threadIdx.x < 64 && s0 + (int)threadIdx.x < a.n_seq) {
+            double cs = 0.0;
+#pragma unroll 8
+            for (int nl = 0; nl < 64; ++nl) cs += t[nl][threadIdx.x];
+            tile_sums[(size_t)tx * a.n_seq + s0 + threadIdx.x] = cs;
+        }
+    }
 }

@@ -338,6 +338,136 @@ extern "C" int mst_fx_biquad_cascade(const float *x, float *y, int n_items, long
     return MST_OK;
 }
 
+// ---- per-item parameters: the equaliser ---------------------------------------------------------------------------
+namespace {
+// the scratch of mst_fx_biquad_cascade_items: the shared call's layout (ends | starts | the shared call's powers, unused here), then one
+// block per item: [M][S] impulse states | [levels][S][S] powers | [MST_MAX_BANDS][5] normalised coefficients
+struct EqItems { int M; long nchunks; size_t shared_bytes; long n_tab, n_pow, stride; };
+EqItems eq_items(int n_items, long L, int C, int n_bands) {
+    EqItems e;
+    e.M = biquad_chunk(L, (long)n_items * C);
+    e.nchunks = (L + e.M - 1) / e.M;
+    e.shared_bytes = mst_fx_biquad_scratch_bytes(n_items, L, C, n_bands);
+    const long S = 2 * n_bands;
+    e.n_tab = (long)e.M * S;
+    e.n_pow = (long)MST_BIQUAD_LEVELS * S * S;
+    e.stride = e.n_tab + e.n_pow + MST_MAX_BANDS * 5;
+    return e;
+}
+}  // namespace
+
+extern "C" size_t mst_fx_biquad_items_scratch_bytes(int n_items, long L, int C, int n_bands) {
+    if (n_items < 1 || L < 1 || C < 1 || n_bands < 1 || n_bands > MST_MAX_BANDS) return 0;
+    const EqItems e = eq_items(n_items, L, C, n_bands);
+    return e.shared_bytes + (size_t)n_items * e.stride * sizeof(double);
+}
+
+extern "C" int mst_fx_biquad_items_plan(int n_items, long L, int C, int n_bands, MstFxBiquadItemsPlan *plan) {
+    if (!plan || plan->struct_size != sizeof(MstFxBiquadItemsPlan)) return fail(MST_ERR_ARG, "mst_fx_biquad_items_plan: MstFxBiquadItemsPlan.struct_size does not match this library's layout");
+    if (n_items < 1 || L < 1 || C < 1 || n_bands < 1 || n_bands > MST_MAX_BANDS) return fail(MST_ERR_ARG, "mst_fx_biquad_items_plan: bad argument");
+    const EqItems e = eq_items(n_items, L, C, n_bands);
+    plan->M = e.M;
+    plan->tables_offset = e.shared_bytes;
+    plan->item_stride = (size_t)e.stride * sizeof(double);
+    plan->powers_offset = (size_t)e.n_tab * sizeof(double);
+    plan->coef_offset = (size_t)(e.n_tab + e.n_pow) * sizeof(double);
+    plan->total_bytes = e.shared_bytes + (size_t)n_items * e.stride * sizeof(double);
+    return MST_OK;
+}
+
+#define MST_BANDS_SWITCH(NB_EXPR, LAUNCH)                                                                                               \
+    switch (NB_EXPR) {                                                                                                                  \
+        case 1: { constexpr int NBv = 1; LAUNCH; } break;                                                                               \
+        case 2: { constexpr int NBv = 2; LAUNCH; } break;                                                                               \
+        case 3: { constexpr int NBv = 3; LAUNCH; } break;                                                                               \
+        case 4: { constexpr int NBv = 4; LAUNCH; } break;                                                                               \
+        case 5: { constexpr int NBv = 5; LAUNCH; } break;                                                                               \
+        case 6: { constexpr int NBv = 6; LAUNCH; } break;                                                                               \
+        case 7: { constexpr int NBv = 7; LAUNCH; } break;                                                                               \
+        default: { constexpr int NBv = 8; LAUNCH; } break;                                                                              \
+    }
+
+extern "C" int mst_fx_biquad_cascade_items(const float *x, float *y, int n_items, long L, int C, const double *coef_dev, int n_bands,
+                                           double *scratch, size_t scratch_bytes, const MstFxFuse *fuse, void *stream) {
+    if (!x || !y || n_items < 1 || n_items > 65535 || L < 1 || C < 1 || (!coef_dev && n_bands > 0)) return fail(MST_ERR_ARG, "mst_fx_biquad_cascade_items: bad argument");
+    if (int rc = fuse_check(fuse, "mst_fx_biquad_cascade_items")) return rc;
+    const bool eq_lane_apply = fuse && (fuse->forms & MST_FX_FORM_EQ_LANE_APPLY);
+    if (fuse && fuse->post_rms) return fail(MST_ERR_UNSUPPORTED, "mst_fx_biquad_cascade_items: tail folding (post_rms) is the imager's");
+    if (fuse && (fuse->out_ms_dev || fuse->in_ms_dev)) return fail(MST_ERR_UNSUPPORTED, "mst_fx_biquad_cascade_items: the mid / side energies travel from the compressor to the imager");
+    if (n_bands < 0 || n_bands > MST_MAX_BANDS) return fail(MST_ERR_UNSUPPORTED, "mst_fx_biquad_cascade_items: at most 8 bands");
+    if (scratch && n_bands > 0) {
+        const EqItems e = eq_items(n_items, L, C, n_bands);
+        if (biquad_time_parallel(e.nchunks, n_bands)) {
+            if (scratch_bytes < e.shared_bytes + (size_t)n_items * e.stride * sizeof(double))
+                return fail(MST_ERR_WORKSPACE, "mst_fx_biquad_cascade_items: scratch too small");
+            const long nchunks = e.nchunks;
+            BiquadChunkArgs a;
+            a.x = x;
+            a.y = y;
+            a.n_seq = n_items * C;
+            a.C = C;
+            a.nchunks = (int)nchunks;
+            a.M = e.M;
+            a.L = L;
+            a.n_bands = n_bands;
+            a.in_scale = fuse ? fuse->in_scale_dev : nullptr;
+            a.out_sumsq = fuse ? fuse->out_sumsq_dev : nullptr;
+            a.out_in_sumsq = fuse ? fuse->out_in_sumsq_dev : nullptr;
+            std::memset(a.coef, 0, sizeof(a.coef));                      // every kernel reads its item's coefficients from the item's block
+            const size_t states = (size_t)a.n_seq * nchunks * 2 * MST_MAX_BANDS;
+            a.ends = scratch;
+            a.starts = scratch + states;
+            FxiEqTabs t;
+            t.base = (double *)((unsigned char *)scratch + e.shared_bytes);
+            t.stride = e.stride;
+            t.off_pow = e.n_tab;
+            t.off_coef = e.n_tab + e.n_pow;
+            t.M = e.M;
+            t.n_bands = n_bands;
+            const unsigned ni = (unsigned)n_items;
+            // every item's tables, built where they are used: no host build, no upload, no cache entry
+            MST_LAUNCH(fxi_eq_tables_kernel, dim3(ni), dim3(64), stream, coef_dev, t);
+            MST_CHECK_LAUNCH("fxi_eq_tables_kernel");
+            const long lanes = (long)C * nchunks;                          // per item
+            if (C == 2) {          // stereo: the VALU state pass on slabs whatever MST_FX_FORM_EQ_VALU_ENDS says (the same bits as the matrix-core one)
+                MST_BANDS_SWITCH(n_bands, MST_LAUNCH(fxi_eq_stereo_ends_kernel<NBv>, dim3((unsigned)((nchunks + 127) / 128), ni), dim3(256), stream, a, t))
+            } else {
+                MST_BANDS_SWITCH(n_bands, MST_LAUNCH(fxi_eq_ends_kernel<NBv>, dim3((unsigned)((4 * lanes + 255) / 256), ni), dim3(256), stream, a, t))
+            }
+            MST_CHECK_LAUNCH("fxi_eq_ends_kernel");
+            const dim3 sg((unsigned)a.n_seq);
+            const double *ends = a.ends;
+            double *starts = scratch + states;
+            if (biquad_scan_threads(nchunks) == 512) {
+                MST_BANDS_SWITCH(n_bands, MST_LAUNCH((fxi_eq_scan_kernel<NBv, 512>), sg, dim3(512), stream, ends, starts, t, C, (int)nchunks))
+            } else {
+                MST_BANDS_SWITCH(n_bands, MST_LAUNCH((fxi_eq_scan_kernel<NBv, 256>), sg, dim3(256), stream, ends, starts, t, C, (int)nchunks))
+            }
+            MST_CHECK_LAUNCH("fxi_eq_scan_kernel");
+            if (C == 2 && !eq_lane_apply) {
+                MST_BANDS_SWITCH(n_bands, MST_LAUNCH(fxi_eq_stereo_apply_kernel<NBv>, dim3((unsigned)((nchunks + 127) / 128), ni), dim3(256), stream, a, t))
+            } else {
+                MST_BANDS_SWITCH(n_bands, MST_LAUNCH(fxi_eq_chunk_apply_kernel<NBv>, dim3((unsigned)((lanes + 63) / 64), ni), dim3(64), stream, a, t))
+            }
+            MST_CHECK_LAUNCH("fxi_eq_apply_kernel");
+            return MST_OK;
+        }
+    }
+    if (fuse && (fuse->in_scale_dev || fuse->out_sumsq_dev || fuse->out_in_sumsq_dev))
+        return fail(MST_ERR_UNSUPPORTED, "mst_fx_biquad_cascade_items: chain fusion needs the time-parallel path (scratch, more than one chunk, >= 1 band)");
+    BiquadArgs a;
+    a.x = x;
+    a.y = y;
+    a.n_seq = n_items * C;
+    a.C = C;
+    a.L = L;
+    a.n_bands = n_bands;
+    std::memset(a.coef, 0, sizeof(a.coef));
+    MST_LAUNCH(fxi_eq_serial_kernel, dim3((unsigned)((a.n_seq + 63) / 64)), dim3(64), stream, a, coef_dev);
+    MST_CHECK_LAUNCH("fxi_eq_serial_kernel");
+    return MST_OK;
+}
+
 namespace {
 // scratch = level differences [L][n_seq] (serial fallback only) | chunk maps [n_seq][nchunks][NP + 1] | chunk start values
 // [nchunks][n_seq] | log10 table [256] | carry [n_seq] | energy partials of the apply pass [ceil(L / 64)][max(n_seq, 3 n_items)]
@@ -476,14 +606,29 @@ FxSide *fx_side() {
     return sides[dev];
 }
 
-int compressor_run(CompArgs a, int n_items, long L, int C, double *scratch, size_t scratch_bytes, void *stream, bool slice_small = false) {
+// items: mst_fx_compressor_items - attack / release coefficients and slope rows per item from the prepared table (every item vetted by
+// mst_fx_compressor_items_prepare: no serial-only dispatch here), the same launches with the per-item kernels
+// the slope of the piece at sorted position p of a chunk map and its reciprocal; [0]: a chunk of T steps, [1]: a last chunk of n_last steps
+void comp_slopes(double aA, double aR, int n_last, double (*slope)[MST_COMP_NP], double (*inv_slope)[MST_COMP_NP]) {
+    for (int which = 0; which < 2; ++which) {
+        const int n = which ? n_last : MST_COMP_T;
+        for (int p = 0; p < MST_COMP_NP; ++p) {
+            slope[which][p] = p <= n ? std::pow(aA, n - p) * std::pow(aR, p) : 0.0;
+            inv_slope[which][p] = p <= n ? 1.0 / slope[which][p] : 0.0;
+        }
+    }
+}
+
+int compressor_run(CompArgs a, int n_items, long L, int C, double *scratch, size_t scratch_bytes, void *stream, bool slice_small = false,
+                   const FxiCmpTab *items = nullptr) {
     // the time-parallel smoother only where its chunk maps are well conditioned (one host comparison, comp_well_conditioned); beyond, the plain
     // call runs one wave per sequence; a call that form cannot serve (chain fusion, parameter grid) is refused, never answered with garbage
-    const bool serial_only = (L + MST_COMP_T - 1) / MST_COMP_T >= 4 && !comp_well_conditioned(a.alpha_att, a.alpha_rel, L);
+    const bool serial_only = !items && (L + MST_COMP_T - 1) / MST_COMP_T >= 4 && !comp_well_conditioned(a.alpha_att, a.alpha_rel, L);
     if (serial_only && (a.thr_items || a.in_scale || a.out_sumsq))
         return fail(MST_ERR_UNSUPPORTED, comp_refusal(a.thr_items ? "mst_fx_compressor_grid" : "mst_fx_compressor", a.alpha_att, a.alpha_rel, L));
     if (!scratch || serial_only) {
-        MST_LAUNCH(fx_compressor_kernel, dim3((a.n_seq + 3) / 4), dim3(256), stream, a);
+        if (items) MST_LAUNCH(fxi_cmp_serial_kernel, dim3((a.n_seq + 3) / 4), dim3(256), stream, a, *items);
+        else MST_LAUNCH(fx_compressor_kernel, dim3((a.n_seq + 3) / 4), dim3(256), stream, a);
         MST_CHECK_LAUNCH("fx_compressor_kernel");
         return MST_OK;
     }
@@ -504,7 +649,8 @@ int compressor_run(CompArgs a, int n_items, long L, int C, double *scratch, size
     if (cs.nchunks < 4) {                               // very short signals: level differences, serial smoother, gain application
         MST_LAUNCH(fx_comp_gain_kernel, tiles, dim3(256), stream, a, scratch);
         MST_CHECK_LAUNCH("fx_comp_gain_kernel");
-        MST_LAUNCH(fx_comp_smooth_kernel, dim3((a.n_seq + 63) / 64), dim3(64), stream, a, scratch);
+        if (items) MST_LAUNCH(fxi_cmp_smooth_kernel, dim3((a.n_seq + 63) / 64), dim3(64), stream, a, scratch, *items);
+        else MST_LAUNCH(fx_comp_smooth_kernel, dim3((a.n_seq + 63) / 64), dim3(64), stream, a, scratch);
         MST_CHECK_LAUNCH("fx_comp_smooth_kernel");
         MST_LAUNCH((fx_comp_apply_kernel<false>), tiles, dim3(256), stream, a, (const double *)scratch, (const double *)nullptr, 0, 0, tsums);
         MST_CHECK_LAUNCH("fx_comp_apply_kernel");
@@ -525,13 +671,7 @@ int compressor_run(CompArgs a, int n_items, long L, int C, double *scratch, size
     m.use_min = a.alpha_att > a.alpha_rel ? 1 : 0;
     // the piece at sorted position p of a chunk of n steps has been through n - p attack and p release steps
     const int n_last = (int)(L - (cs.nchunks - 1) * MST_COMP_T);
-    for (int which = 0; which < 2; ++which) {
-        const int n = which ? n_last : MST_COMP_T;
-        for (int p = 0; p < MST_COMP_NP; ++p) {
-            m.slope[which][p] = p <= n ? std::pow(m.aA, n - p) * std::pow(m.aR, p) : 0.0;
-            m.inv_slope[which][p] = p <= n ? 1.0 / m.slope[which][p] : 0.0;
-        }
-    }
+    comp_slopes(m.aA, m.aR, n_last, m.slope, m.inv_slope);
     m.ycarry = (double *)((unsigned char *)scratch + cs.xl + cs.maps + cs.ystart + cs.tab);
     // Time slices.  The chain is ONE dependent walk per sequence (n_seq workgroups, latency-bound: most of the chip idles beside it) while
     // the map and apply kernels are throughput work.  The signal is cut into FX_SLICES (three) slices of whole chain batches; the caller's
@@ -552,7 +692,8 @@ int compressor_run(CompArgs a, int n_items, long L, int C, double *scratch, size
         mm.chunk0 = b0 * MST_CHAIN_CB;
         const long c1 = std::min<long>((long)b1 * MST_CHAIN_CB, cs.nchunks);
         const dim3 cg((unsigned)(c1 - mm.chunk0), (unsigned)gy);
-        if (m.use_min) MST_LAUNCH(fx_comp_map_kernel<true>, cg, dim3(64), st, mm, a);
+        if (items) MST_LAUNCH(fxi_cmp_map_kernel, cg, dim3(64), st, mm, a, *items);
+        else if (m.use_min) MST_LAUNCH(fx_comp_map_kernel<true>, cg, dim3(64), st, mm, a);
         else MST_LAUNCH(fx_comp_map_kernel<false>, cg, dim3(64), st, mm, a);
         MST_CHECK_LAUNCH("fx_comp_map_kernel");
         return MST_OK;
@@ -561,13 +702,15 @@ int compressor_run(CompArgs a, int n_items, long L, int C, double *scratch, size
         CompMapArgs mm = m;
         mm.batch0 = b0;
         mm.batch1 = b1;
-        MST_LAUNCH(fx_comp_chain_kernel, dim3(a.n_seq), dim3(MST_CHAIN_THREADS), st, mm);
+        if (items) MST_LAUNCH(fxi_cmp_chain_kernel, dim3(a.n_seq), dim3(MST_CHAIN_THREADS), st, mm, *items);
+        else MST_LAUNCH(fx_comp_chain_kernel, dim3(a.n_seq), dim3(MST_CHAIN_THREADS), st, mm);
         MST_CHECK_LAUNCH("fx_comp_chain_kernel");
         return MST_OK;
     };
     auto launch_apply = [&](int b0, int b1, void *st) -> int {      // a batch is 32 chunks = 16 time tiles of 64 samples
         const long t0 = (long)b0 * (MST_CHAIN_CB / 2), t1 = std::min<long>((long)b1 * (MST_CHAIN_CB / 2), (long)tiles.x);
-        MST_LAUNCH((fx_comp_apply_kernel<true>), dim3((unsigned)(t1 - t0), tiles.y), dim3(256), st, a, tab, (const double *)m.ystart, m.nchunks, (int)t0, tsums);
+        if (items) MST_LAUNCH((fxi_cmp_apply_kernel<true>), dim3((unsigned)(t1 - t0), tiles.y), dim3(256), st, a, tab, (const double *)m.ystart, m.nchunks, (int)t0, tsums, *items);
+        else MST_LAUNCH((fx_comp_apply_kernel<true>), dim3((unsigned)(t1 - t0), tiles.y), dim3(256), st, a, tab, (const double *)m.ystart, m.nchunks, (int)t0, tsums);
         MST_CHECK_LAUNCH("fx_comp_apply_kernel");
         return MST_OK;
     };
@@ -681,6 +824,87 @@ extern "C" int mst_fx_compressor_grid(const float *x, float *y, int n_items, lon
     return MST_OK;
 }
 
+// ---- per-item parameters: the compressor ---------------------------------------------------------------------------------------------------
+// table (float64): thr [n] | ratio [n] | aA [n] | aR [n] | slope [n][2][NP] | inv_slope [n][2][NP]
+extern "C" size_t mst_fx_compressor_items_table_bytes(int n_items) {
+    return n_items < 1 ? 0 : (size_t)n_items * (4 + 4 * MST_COMP_NP) * sizeof(double);
+}
+
+extern "C" int mst_fx_compressor_items_prepare(const double *params_host, int n_items, long L, int C, double sample_rate, int forms,
+                                               double *table_host, size_t table_bytes, int *first_refused_item) {
+    if (first_refused_item) *first_refused_item = -1;
+    if (!params_host || !table_host || n_items < 1 || L < 1 || C < 1 || sample_rate <= 0) return fail(MST_ERR_ARG, "mst_fx_compressor_items_prepare: bad argument");
+    if (forms & ~(MST_FX_FORM_EQ_LANE_APPLY | MST_FX_FORM_EQ_VALU_ENDS | MST_FX_FORM_COMP_SLICE_SMALL)) return fail(MST_ERR_ARG, "mst_fx_compressor_items_prepare: unknown forms bits");
+    if (table_bytes < mst_fx_compressor_items_table_bytes(n_items)) return fail(MST_ERR_WORKSPACE, "mst_fx_compressor_items_prepare: table too small");
+    const long nchunks = (L + MST_COMP_T - 1) / MST_COMP_T;
+    const int n_last = (int)(L - (nchunks - 1) * MST_COMP_T);
+    const size_t n = (size_t)n_items;
+    double *thr = table_host, *ratio = thr + n, *aA = ratio + n, *aR = aA + n, *slope = aR + n, *inv = slope + n * 2 * MST_COMP_NP;
+    for (int i = 0; i < n_items; ++i) {
+        const double *p = params_host + 4 * (size_t)i;
+        char buf[160];
+        if (!(p[1] > 0) || !(p[2] > 0) || !(p[3] > 0)) {
+            std::snprintf(buf, sizeof(buf), "mst_fx_compressor_items_prepare: item %d: attack, release and ratio must be positive", i);
+            if (first_refused_item) *first_refused_item = i;
+            return fail(MST_ERR_ARG, buf);
+        }
+        if (p[0] == 0.0 && p[3] == 1.0) {          // Compressor.process returns its input for this pair (:637): not a compressor call
+            std::snprintf(buf, sizeof(buf), "mst_fx_compressor_items_prepare: item %d is the bypass (threshold 0 dB, ratio 1): leave it out of the batch", i);
+            if (first_refused_item) *first_refused_item = i;
+            return fail(MST_ERR_UNSUPPORTED, buf);
+        }
+        thr[i] = p[0];
+        ratio[i] = p[3];
+        aA[i] = comp_alpha(sample_rate, p[1]);
+        aR[i] = comp_alpha(sample_rate, p[2]);
+        if (nchunks >= 4 && !comp_well_conditioned(aA[i], aR[i], L)) {          // mst_fx_compressor_plan's rule, per item
+            if (first_refused_item) *first_refused_item = i;
+            std::snprintf(buf, sizeof(buf), "mst_fx_compressor_items_prepare: item %d", i);
+            return fail(MST_ERR_UNSUPPORTED, comp_refusal(buf, aA[i], aR[i], L));
+        }
+        comp_slopes(aA[i], aR[i], n_last, (double (*)[MST_COMP_NP])(slope + (size_t)i * 2 * MST_COMP_NP), (double (*)[MST_COMP_NP])(inv + (size_t)i * 2 * MST_COMP_NP));
+    }
+    return MST_OK;
+}
+
+extern "C" int mst_fx_compressor_items(const float *x, float *y, int n_items, long L, int C, const double *table_dev, double *scratch,
+                                       size_t scratch_bytes, const MstFxFuse *fuse, void *stream) {
+    if (!x || !y || !table_dev || n_items < 1 || L < 1 || C < 1) return fail(MST_ERR_ARG, "mst_fx_compressor_items: bad argument");
+    if (int rc = fuse_check(fuse, "mst_fx_compressor_items")) return rc;
+    const bool fused = fuse && (fuse->in_scale_dev || fuse->out_sumsq_dev);
+    if (fuse && (fuse->post_rms || fuse->out_in_sumsq_dev))
+        return fail(MST_ERR_UNSUPPORTED, "mst_fx_compressor_items: tail folding (post_rms) is the imager's, out_in_sumsq_dev the equaliser's");
+    if (fused && !scratch) return fail(MST_ERR_UNSUPPORTED, "mst_fx_compressor_items: chain fusion needs the scratch buffer");
+    if (fuse && fuse->in_ms_dev) return fail(MST_ERR_UNSUPPORTED, "mst_fx_compressor_items: in_ms_dev is the imager's");
+    const size_t n = (size_t)n_items;
+    CompArgs a;
+    a.x = x;
+    a.y = y;
+    a.n_seq = n_items * C;
+    a.C = C;
+    a.L = L;
+    a.threshold = 0.0;
+    a.ratio = 1.0;
+    a.thr_items = table_dev;
+    a.ratio_items = table_dev + n;
+    a.alpha_att = 0.0;          // per item: FxiCmpTab
+    a.alpha_rel = 0.0;
+    a.makeup = 0.0;
+    a.in_scale = fuse ? fuse->in_scale_dev : nullptr;
+    a.out_sumsq = fuse ? fuse->out_sumsq_dev : nullptr;
+    if (fuse && fuse->out_ms_dev) {
+        if (C != 2 || !fuse->out_sumsq_dev) return fail(MST_ERR_UNSUPPORTED, "mst_fx_compressor_items: out_ms_dev needs stereo audio and out_sumsq_dev");
+        a.out_ms = fuse->out_ms_dev;
+    }
+    FxiCmpTab t;
+    t.aA = table_dev + 2 * n;
+    t.aR = table_dev + 3 * n;
+    t.slope = table_dev + 4 * n;
+    t.inv = t.slope + n * 2 * MST_COMP_NP;
+    t.C = C;
+    return compressor_run(a, n_items, L, C, scratch, scratch_bytes, stream, fuse && (fuse->forms & MST_FX_FORM_COMP_SLICE_SMALL), &t);
+}
+
 extern "C" int mst_fx_range_reduce(const float *x, long L, int C, int channel, const int *item_dev, const long *lo_dev,
                                    const long *hi_dev, int n_ranges, int mode, double *out_dev, void *stream) {
     if (!x || !item_dev || !lo_dev || !hi_dev || !out_dev || L < 1 || C < 1 || channel < 0 || channel >= C || n_ranges < 1 ||
@@ -754,12 +978,49 @@ extern "C" int mst_fx_gain(const float *x, float *y, int n_items, long L, int C,
     if (int rc = fuse_check(fuse, "mst_fx_gain")) return rc;
     if (fuse && (fuse->post_rms || fuse->out_in_sumsq_dev || fuse->out_ms_dev || fuse->in_ms_dev))
         return fail(MST_ERR_UNSUPPORTED, "mst_fx_gain: tail folding (post_rms) is the imager's, out_in_sumsq_dev the equaliser's, the mid / side energies the compressor's / imager's");
-    double g = std::pow(10.0, gain_db / 20.0);
-    if (invert) g = -g;
     const long per = L * C;
-    MST_LAUNCH(fx_scale_kernel, dim3((unsigned)((per + 255) / 256), n_items), dim3(256), stream, x, y, per, (float)g,
+    MST_LAUNCH(fx_scale_kernel, dim3((unsigned)((per + 255) / 256), n_items), dim3(256), stream, x, y, per, fx_gain_factor(gain_db, invert),
                (const double *)nullptr, (const double *)nullptr, 0, per, fuse ? fuse->in_scale_dev : (const double *)nullptr);
     MST_CHECK_LAUNCH("fx_scale_kernel");
+    return MST_OK;
+}
+
+extern "C" int mst_fx_midside_imager_items(const float *x, float *y, int n_items, long L, const double *bal_dev, double *scratch,
+                                           const float *post_gain_dev, const MstFxFuse *fuse, void *stream) {
+    if (!x || !y || !scratch || !bal_dev || n_items < 1 || n_items > 65535 || L < 1) return fail(MST_ERR_ARG, "mst_fx_midside_imager_items: bad argument");
+    if (int rc = fuse_check(fuse, "mst_fx_midside_imager_items")) return rc;
+    const bool fold = fuse && fuse->post_rms;
+    if (fuse && fuse->out_in_sumsq_dev) return fail(MST_ERR_UNSUPPORTED, "mst_fx_midside_imager_items: out_in_sumsq_dev is the equaliser's");
+    if (fold && !fuse->in_sumsq_dev) return fail(MST_ERR_ARG, "mst_fx_midside_imager_items: post_rms needs in_sumsq_dev");
+    if (fuse && fuse->out_ms_dev) return fail(MST_ERR_UNSUPPORTED, "mst_fx_midside_imager_items: out_ms_dev is the compressor's");
+    int chunks = (int)std::min<long>(MST_SUMSQ_SLOTS, (L + 8191) / 8192);
+    if (chunks < 1) chunks = 1;
+    const double *parts = scratch;
+    if (fuse && fuse->in_ms_dev) {
+        parts = fuse->in_ms_dev;
+        chunks = MST_SUMSQ_SLOTS;
+    } else {
+        MST_LAUNCH(fx_energy_parts_kernel, dim3(n_items * chunks), dim3(256), stream, x, scratch, L, chunks);
+        MST_CHECK_LAUNCH("fx_energy_parts_kernel");
+    }
+    MST_LAUNCH(fxi_imager_apply_kernel, dim3((unsigned)((L + MST_IMAGER_FRAMES - 1) / MST_IMAGER_FRAMES), n_items), dim3(256), stream, x, y,
+               parts, chunks, L, bal_dev, fuse ? fuse->in_scale_dev : (const double *)nullptr,
+               fuse ? fuse->out_sumsq_dev : (double *)nullptr, fold ? fuse->in_sumsq_dev : (const double *)nullptr,
+               fold ? post_gain_dev : (const float *)nullptr, fold ? fuse->post_gain : 1.0f);
+    MST_CHECK_LAUNCH("fxi_imager_apply_kernel");
+    return MST_OK;
+}
+
+extern "C" int mst_fx_gain_items(const float *x, float *y, int n_items, long L, int C, const double *gain_db_dev, const int *invert_dev,
+                                 const MstFxFuse *fuse, void *stream) {
+    if (!x || !y || !gain_db_dev || n_items < 1 || n_items > 65535 || L < 1 || C < 1) return fail(MST_ERR_ARG, "mst_fx_gain_items: bad argument");
+    if (int rc = fuse_check(fuse, "mst_fx_gain_items")) return rc;
+    if (fuse && (fuse->post_rms || fuse->out_in_sumsq_dev || fuse->out_ms_dev || fuse->in_ms_dev))
+        return fail(MST_ERR_UNSUPPORTED, "mst_fx_gain_items: tail folding (post_rms) is the imager's, out_in_sumsq_dev the equaliser's, the mid / side energies the compressor's / imager's");
+    const long per = L * C;
+    MST_LAUNCH(fxi_gain_kernel, dim3((unsigned)((per + 255) / 256), n_items), dim3(256), stream, x, y, per, gain_db_dev, invert_dev,
+               fuse ? fuse->in_scale_dev : (const double *)nullptr);
+    MST_CHECK_LAUNCH("fxi_gain_kernel");
     return MST_OK;
 }
 

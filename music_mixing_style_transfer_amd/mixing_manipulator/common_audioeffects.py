@@ -126,10 +126,34 @@ class _Dev:
         self._keep = (f, in_scale, sumsq, in_sumsq, self.last_in_sumsq, self.last_ms, in_ms)    # alive until the launches are queued
         return C.byref(f), sumsq
 
+    def upload(self, a):
+        """A small host array of per-item parameters on this call's device: from pinned memory, not waited for (the caching host allocator keeps
+        the pinned block until the copy has run)."""
+        t = torch.from_numpy(np.ascontiguousarray(a))
+        if self.x.is_cuda:
+            return t.pin_memory().to(self.x.device, non_blocking=True)
+        return self.lib.to_device(t)
+
     def out(self, y):
         if not self.batched:
             y = y[0]
         return y.cpu().numpy() if self.numpy else y
+
+
+def parameter_values(processor):
+    """{name: value} of a processor's parameters: the per-item record of AugmentationChain.call_items and of process_items."""
+    return {p.name: p.value for p in processor.parameters}
+
+
+def _value(processor, values, name):
+    return values[name] if values is not None and name in values else getattr(processor.parameters, name).value
+
+
+def _items_dev(x, values):
+    d = _Dev(x)
+    if not d.batched or d.n != len(values):
+        raise ValueError(f"process_items: x must be a batch [n_items, L, C] with one dict of parameter values per item (got {tuple(d.x.shape)}, {len(values)} dicts)")
+    return d
 
 
 def rms_normalize_(x, y):
@@ -191,15 +215,16 @@ class Equaliser(Processor):
         self.bands = list(bands)
         self.hard_clip = hard_clip
 
-    def coefficients(self):
+    def coefficients(self, values=None):
+        """[n_bands][6] float64 of the current parameter values, or of `values` ({name: value}; names it lacks keep their current value)"""
         rows = []
         for band in self.bands:
-            g = getattr(self.parameters, band + "_gain").value
-            fc = getattr(self.parameters, band + "_freq").value
+            g = _value(self, values, band + "_gain")
+            fc = _value(self, values, band + "_freq")
             if band in ("low_shelf", "high_shelf"):
                 rows.append(rbj_coefficients(band, g, 0.707, fc, self.sample_rate))
             else:
-                rows.append(rbj_coefficients("peaking", g, getattr(self.parameters, band + "_q").value, fc, self.sample_rate))
+                rows.append(rbj_coefficients("peaking", g, _value(self, values, band + "_q"), fc, self.sample_rate))
         return np.asarray(rows, dtype=np.float64)
 
     def reset_state(self):
@@ -222,6 +247,28 @@ class Equaliser(Processor):
         d.lib.check(d.lib.mst_fx_biquad_cascade(d.x.data_ptr(), y.data_ptr(), d.n, d.L, d.C,
                                                 coef.ctypes.data_as(C.POINTER(C.c_double)), coef.shape[0],
                                                 sc.data_ptr(), nbytes, fuse, d.stream), "mst_fx_biquad_cascade")
+        if self.hard_clip:
+            y = y.clamp_(-1.0, 1.0)
+        return y, sumsq
+
+    def process_items(self, x, values):
+        """x [n_items, L, C]; values: one {parameter name: value} per item.  Item i is filtered with the settings of values[i] - one
+        mst_fx_biquad_cascade_items call: the RBJ coefficients of all items on the host (float64, rbj_coefficients), one upload from pinned
+        memory, the time-parallel tables built on the device.  Item i gets the bits of process() with those settings on the same batch."""
+        d = _items_dev(x, values)
+        y, _ = self._run_items(d, values, None, False)
+        return d.out(y)
+
+    def _run_items(self, d, values, in_scale, want_sumsq, want_in_sumsq=False):
+        coef = np.ascontiguousarray(np.stack([self.coefficients(v) for v in values]))            # [n][n_bands][6]
+        nb = coef.shape[1]
+        cd = d.upload(coef)
+        y = torch.empty_like(d.x)
+        nbytes = d.lib.mst_fx_biquad_items_scratch_bytes(d.n, d.L, d.C, nb)
+        sc = d.scratch((nbytes + 7) // 8)
+        fuse, sumsq = d.fuse(in_scale, want_sumsq, want_in_sumsq=want_in_sumsq, forms=getattr(self, "kernel_forms", 0))
+        d.lib.check(d.lib.mst_fx_biquad_cascade_items(d.x.data_ptr(), y.data_ptr(), d.n, d.L, d.C, cd.data_ptr(), nb,
+                                                      sc.data_ptr(), nbytes, fuse, d.stream), "mst_fx_biquad_cascade_items")
         if self.hard_clip:
             y = y.clamp_(-1.0, 1.0)
         return y, sumsq
@@ -273,6 +320,66 @@ class Compressor(Processor):
                                             float(self.sample_rate), sc.data_ptr(), nbytes, fuse, d.stream), "mst_fx_compressor")
         return y, sumsq
 
+    def _prepare_items(self, d, values):
+        """The table mst_fx_compressor_items reads for these items, on its way to the device from pinned memory -> (table, -1); or (None, i):
+        item i cannot take part (attack / release beyond the time-parallel smoother's conditioning limit, or the bypass pair)."""
+        params = np.ascontiguousarray([[float(_value(self, v, k)) for k in ("threshold", "attack_time", "release_time", "ratio")] for v in values], dtype=np.float64)
+        nbytes = d.lib.mst_fx_compressor_items_table_bytes(len(values))
+        table = torch.empty(nbytes // 8, dtype=torch.float64)
+        if d.x.is_cuda:
+            table = table.pin_memory()
+        refused = C.c_int(-1)
+        rc = d.lib.mst_fx_compressor_items_prepare(params.ctypes.data, len(values), d.L, d.C, float(self.sample_rate), getattr(self, "kernel_forms", 0),
+                                                   table.data_ptr(), nbytes, C.byref(refused))
+        if rc != 0 and refused.value >= 0:
+            return None, refused.value
+        d.lib.check(rc, "mst_fx_compressor_items_prepare")
+        return (table.to(d.x.device, non_blocking=True) if d.x.is_cuda else d.lib.to_device(table)), -1
+
+    def process_items(self, x, values):
+        """x [n_items, L, C]; values: one {parameter name: value} per item - one mst_fx_compressor_items call for the items its prepare step
+        accepts; an item it refuses (ill-conditioned attack / release pair, or the bypass) runs alone through process() with its values."""
+        d = _items_dev(x, values)
+        xs = d.x
+        batch, alone = list(range(d.n)), []
+        table = None
+        while batch:
+            table, r = self._prepare_items(d.rebind(xs[batch] if len(batch) < xs.shape[0] else xs), [values[i] for i in batch])
+            if table is not None:
+                break
+            alone.append(batch.pop(r))
+        y = torch.empty_like(xs)
+        if batch:
+            yb, _ = self._run_items(d, [values[i] for i in batch], None, False, table=table)
+            if len(batch) == xs.shape[0]:
+                y = yb
+            else:
+                y[batch] = yb
+        keep = parameter_values(self)
+        try:
+            for i in alone:
+                for k, val in values[i].items():
+                    getattr(self.parameters, k).value = val
+                y[i:i + 1] = self.process(xs[i:i + 1])
+        finally:
+            for k, val in keep.items():
+                getattr(self.parameters, k).value = val
+        d.rebind(xs)
+        return d.out(y)
+
+    def _run_items(self, d, values, in_scale, want_sumsq, table=None):
+        if table is None:
+            table, r = self._prepare_items(d, values)
+            if table is None:
+                raise NotImplementedError(f"Compressor: item {r} cannot run in a per-item batch: " + d.lib.mst_last_error().decode())
+        y = torch.empty_like(d.x)
+        nbytes = d.lib.mst_fx_compressor_scratch_bytes(d.n, d.L, d.C)
+        sc = d.scratch((nbytes + 7) // 8)
+        fuse, sumsq = d.fuse(in_scale, want_sumsq, want_ms=bool(want_sumsq and d.C == 2), forms=getattr(self, "kernel_forms", 0))
+        d.lib.check(d.lib.mst_fx_compressor_items(d.x.data_ptr(), y.data_ptr(), d.n, d.L, d.C, table.data_ptr(), sc.data_ptr(), nbytes,
+                                                  fuse, d.stream), "mst_fx_compressor_items")
+        return y, sumsq
+
     def update(self, parameter_name=None):
         self.yL_prev = None
 
@@ -305,6 +412,25 @@ class MidSideImager(Processor):
                                                 sc.data_ptr(), fuse, d.stream), "mst_fx_midside_imager")
         return y, sumsq
 
+    def process_items(self, x, values):
+        """x [n_items, L, 2]; values: one {'bal': value} per item - one mst_fx_midside_imager_items call"""
+        d = _items_dev(x, values)
+        y, _ = self._run_items(d, [_value(self, v, "bal") for v in values], None, False)
+        return d.out(y)
+
+    def _run_items(self, d, bals, in_scale, want_sumsq, in_sumsq=None, post_gains=None, in_ms=None):
+        """bals: one balance per item; post_gains (tail folding, with in_sumsq): one float32 factor per item"""
+        if d.C != 2:
+            raise ValueError("MidSideImager needs stereo audio [L, 2]")
+        y = torch.empty_like(d.x)
+        sc = d.scratch(2 * SUMSQ_SLOTS * d.n)
+        bd = d.upload(np.asarray(bals, dtype=np.float64))
+        gd = d.upload(np.asarray(post_gains, dtype=np.float32)) if post_gains is not None else None
+        fuse, sumsq = d.fuse(in_scale, want_sumsq, in_sumsq, 1.0 if post_gains is not None else None, in_ms=in_ms)
+        d.lib.check(d.lib.mst_fx_midside_imager_items(d.x.data_ptr(), y.data_ptr(), d.n, d.L, bd.data_ptr(), sc.data_ptr(),
+                                                      gd.data_ptr() if gd is not None else None, fuse, d.stream), "mst_fx_midside_imager_items")
+        return y, sumsq
+
 
 class Gain(Processor):
     """Gain in dB, optional polarity inversion."""
@@ -324,16 +450,31 @@ class Gain(Processor):
     def fusable(self, d):
         return True
 
-    def factor(self):
+    def factor(self, values=None):
         """The float32 multiplier mst_fx_gain applies: float(10 ** (gain_db / 20)), negated when inverting."""
-        g = math.pow(10.0, float(self.parameters.gain.value) / 20.0)
-        return -g if bool(self.parameters.invert.value) else g
+        g = math.pow(10.0, float(_value(self, values, "gain")) / 20.0)
+        return -g if bool(_value(self, values, "invert")) else g
 
     def _run(self, d, in_scale, want_sumsq):
         y = torch.empty_like(d.x)
         fuse, _ = d.fuse(in_scale, False)              # a gain leaves no energy sum behind (nothing downstream asks for one cheaply)
         d.lib.check(d.lib.mst_fx_gain(d.x.data_ptr(), y.data_ptr(), d.n, d.L, d.C, float(self.parameters.gain.value),
                                       int(bool(self.parameters.invert.value)), fuse, d.stream), "mst_fx_gain")
+        return y, None
+
+    def process_items(self, x, values):
+        """x [n_items, L, C]; values: one {'gain': dB, 'invert': bool} per item - one mst_fx_gain_items call"""
+        d = _items_dev(x, values)
+        y, _ = self._run_items(d, values, None, False)
+        return d.out(y)
+
+    def _run_items(self, d, values, in_scale, want_sumsq):
+        y = torch.empty_like(d.x)
+        gd = d.upload(np.asarray([float(_value(self, v, "gain")) for v in values], dtype=np.float64))
+        iv = d.upload(np.asarray([int(bool(_value(self, v, "invert"))) for v in values], dtype=np.int32))
+        fuse, _ = d.fuse(in_scale, False)
+        d.lib.check(d.lib.mst_fx_gain_items(d.x.data_ptr(), y.data_ptr(), d.n, d.L, d.C, gd.data_ptr(), iv.data_ptr(), fuse, d.stream),
+                    "mst_fx_gain_items")
         return y, None
 
 
@@ -561,10 +702,12 @@ def _sumsq(d, t):
 class _Pending:
     """An array on its way through an AugmentationChain: device batch t [n, L, C], the per-item factor still to be applied to it
     (scale, float64 [n] or None) and sum(t^2) per item when its producer left it behind (sumsq, float64 [n] or None)."""
-    __slots__ = ("dev", "t", "scale", "sumsq", "deferred", "ms")
+    __slots__ = ("dev", "t", "scale", "sumsq", "deferred", "ms", "members", "mat")
 
     def __init__(self, dev, t, scale, sumsq, deferred=None, ms=None):
         self.dev, self.t, self.scale, self.sumsq = dev, t, scale, sumsq
+        self.members = None     # call_items: the items of the batch, in row order; mat: its materialised batch once somebody needed it
+        self.mat = None
         self.ms = ms            # mid / side energies of t left behind by its producer (the compressor), or None
         # deferred = (imager, bal): an rms-normalised MidSideImager step that has NOT run yet - if a Gain is next, the imager's pass
         # applies the rms factor and the gain itself (MstFxFuse tail folding); anything else runs it first (flush)
@@ -577,10 +720,17 @@ class _Pending:
         imager, bal = self.deferred
         d = self.dev.rebind(self.t)
         sumsq_x = self.sumsq if self.sumsq is not None else _sumsq(d, self.t)
+        items = isinstance(bal, (list, tuple))          # call_items: one balance (and one gain) per item
         if gain is not None:
-            y, _ = imager._run(d, self.scale, False, bal=bal, in_sumsq=sumsq_x, post_gain=gain, in_ms=self.ms)
+            if items:
+                y, _ = imager._run_items(d, bal, self.scale, False, in_sumsq=sumsq_x, post_gains=gain, in_ms=self.ms)
+            else:
+                y, _ = imager._run(d, self.scale, False, bal=bal, in_sumsq=sumsq_x, post_gain=gain, in_ms=self.ms)
             return _Pending(d, y, None, None)
-        y, sumsq_y = imager._run(d, self.scale, True, bal=bal, in_ms=self.ms)
+        if items:
+            y, sumsq_y = imager._run_items(d, bal, self.scale, True, in_ms=self.ms)
+        else:
+            y, sumsq_y = imager._run(d, self.scale, True, bal=bal, in_ms=self.ms)
         scale = torch.empty(d.n, dtype=torch.float64, device=y.device)
         d.lib.check(d.lib.mst_fx_rms_pending(self.scale.data_ptr() if self.scale is not None else None, sumsq_x.data_ptr(),
                                              self.t.shape[1] * self.t.shape[2], sumsq_y.data_ptr(), y.shape[1] * y.shape[2],
@@ -687,6 +837,204 @@ class AugmentationChain:
             w = self.parallel_weight_factor if self.parallel_weight_factor else np.random.rand() / 2.0
             y_list = [w * x + (1 - w) * y for x, y in zip(x_list, y_list)]
         return y_list
+
+    # ------------------------------------------------------------------------------------------ one batch, item i with its own draws
+    # call_items(x) gives item i of x [n, L, C] what `self([x[i]])[0]` returns in the loop `for i in range(n)`: the loop's draws from
+    # `random` and `np.random`, in the loop's order (no draw depends on the audio), are taken first - the plan - and the audio work follows,
+    # batched over the items that meet in the same processor.
+
+    def _plan_one(self, channels):
+        """The draws of ONE __call__ on an array with `channels` channels -> (ops, channels of the result).  ops: ("begin",) at the start of a
+        parallel chain (its input is kept), ("fx", processor, {name: value}, rms_normalize, extra) per applied processor, ("mix", w) at the
+        end of a parallel chain.  Nested chains are laid out flat, in the order their __call__ runs."""
+        ops = []
+        if self.shuffle:
+            random.shuffle(self.fxs)
+        if self.parallel:
+            ops.append(("begin",))
+        for fx, p, rms in self.fxs:
+            if np.random.rand() < p:
+                if isinstance(fx, Processor):
+                    if fx.block_size is not None:
+                        raise NotImplementedError("block-wise processors are not on the gfx950 path")
+                    if self.randomize_param_value:
+                        fx.randomize()
+                    else:
+                        fx.update(None)
+                    extra = None
+                    if isinstance(fx, ConvolutionalReverb):          # process() adapts the response to the channel count - with a draw for mono audio
+                        if not hasattr(fx, "h"):
+                            fx.update()
+                        if fx.h.shape[1] == 1 and channels > 1:
+                            fx.h = np.hstack([fx.h] * channels)
+                        if fx.h.shape[1] > 1 and channels == 1:
+                            fx.h = fx.h[:, np.random.randint(fx.h.shape[1]), np.newaxis]
+                        extra = fx.h
+                    elif isinstance(fx, (Panner, Haas, AlgorithmicReverb)):
+                        channels = 2
+                    ops.append(("fx", fx, parameter_values(fx), rms, extra))
+                else:
+                    sub, channels = fx._plan_one(channels)
+                    ops.extend(sub)
+        if self.parallel:
+            w = self.parallel_weight_factor if self.parallel_weight_factor else np.random.rand() / 2.0
+            ops.append(("mix", w))
+        return ops, channels
+
+    def plan_items(self, n, channels):
+        """The plans of `for i in range(n): self([x[i]])` on arrays with `channels` channels: that loop's draws from `random` and `np.random`,
+        in its order - both generators, every `fxs` order and every parameter value are left as the loop leaves them."""
+        return [self._plan_one(channels)[0] for _ in range(n)]
+
+    def _processors(self):
+        for fx, _, _ in self.fxs:
+            if isinstance(fx, Processor):
+                yield fx
+            else:
+                yield from fx._processors()
+
+    @staticmethod
+    def _restore(fx, values, extra):
+        for k, v in values.items():
+            getattr(fx.parameters, k).value = v
+        if isinstance(fx, ConvolutionalReverb):
+            if extra is not None:
+                fx.h = extra          # the response as the plan adapted it: process() then draws nothing
+        else:
+            fx.update(None)
+
+    def _apply_items(self, x, fx, values, rms, extras):
+        """apply_processor for a _Pending batch whose item r runs `fx` with values[r]"""
+        per_item = isinstance(fx, (Equaliser, Compressor, MidSideImager, Gain))
+        if x.deferred is not None:
+            if isinstance(fx, Gain) and not rms:
+                return x.flush(gain=[fx.factor(v) for v in values])
+            x = x.flush()
+        d = x.dev.rebind(x.t)
+        if isinstance(fx, MidSideImager) and rms and fx.fusable(d):
+            return _Pending(d, x.t, x.scale, x.sumsq, deferred=(fx, [float(v["bal"]) for v in values]), ms=x.ms)
+        table = fx._prepare_items(d, values)[0] if isinstance(fx, Compressor) else None          # None: an item its prepare step refuses
+        if per_item and (table is not None if isinstance(fx, Compressor) else fx.fusable(d)):
+            d.last_in_sumsq = None
+            d.last_ms = None
+            if isinstance(fx, Compressor):
+                y, sumsq_y = fx._run_items(d, values, x.scale, rms, table=table)
+            elif isinstance(fx, Equaliser):
+                y, sumsq_y = fx._run_items(d, values, x.scale, rms, want_in_sumsq=rms and x.sumsq is None)
+            elif isinstance(fx, MidSideImager):
+                y, sumsq_y = fx._run_items(d, [float(v["bal"]) for v in values], x.scale, rms)
+            else:
+                y, sumsq_y = fx._run_items(d, values, x.scale, rms)
+            ms = getattr(d, "last_ms", None)
+            if not rms:
+                return _Pending(d, y, None, sumsq_y, ms=ms)
+            sumsq_x = x.sumsq if x.sumsq is not None else (d.last_in_sumsq if d.last_in_sumsq is not None else _sumsq(d, x.t))
+            if sumsq_y is None:
+                sumsq_y = _sumsq(d, y)
+            scale = torch.empty(d.n, dtype=torch.float64, device=y.device)
+            d.lib.check(d.lib.mst_fx_rms_pending(x.scale.data_ptr() if x.scale is not None else None, sumsq_x.data_ptr(),
+                                                 x.t.shape[1] * x.t.shape[2], sumsq_y.data_ptr(), y.shape[1] * y.shape[2],
+                                                 scale.data_ptr(), d.n, d.stream), "mst_fx_rms_pending")
+            return _Pending(d, y, scale, sumsq_y, ms=ms)
+        xm = x.materialize()
+        if per_item:          # outside the fusion (a short signal, a hard-clipping equaliser, a compressor item to run alone): process_items
+            y = fx.process_items(xm, values)
+        else:                 # no per-item form (panner, Haas, the reverbs): item by item through process()
+            ys = []
+            for r, (v, e) in enumerate(zip(values, extras)):
+                self._restore(fx, v, e)
+                yr = fx.process(xm[r:r + 1])
+                ys.append(yr if yr.dim() == 3 else yr[None])
+            y = torch.cat(ys, 0)
+        if rms:
+            y = rms_normalize_(xm, y)
+        d = _Dev(y)
+        return _Pending(d, d.x, None, None)
+
+    def call_items(self, x):
+        """x: a batch [n, L, C] (tensor or numpy).  Item i receives what `self([x[i]])[0]` returns in the loop `for i in range(n)`, with that
+        loop's draws; processors, generators and `fxs` are left as the loop leaves them.  Returns [n, L, C'] when every item ends with the same
+        channel count (a Panner / Haas / reverb turns mono into stereo for the items it is applied to), else a list of [L, C_i]."""
+        d0 = _Dev(x)
+        if not d0.batched:
+            raise ValueError("call_items: x must be a batch [n_items, L, C]")
+        n = d0.n
+        plans = self.plan_items(n, d0.C)
+        final = [(fx, parameter_values(fx), getattr(fx, "h", None)) for fx in self._processors()]
+        try:
+            rows = self._execute_items(d0, plans)
+        finally:
+            for fx, values, h in final:
+                self._restore(fx, values, h)
+        if isinstance(rows, torch.Tensor):
+            out = rows
+        elif len({tuple(r.shape) for r in rows}) == 1:
+            out = torch.stack(rows, 0)
+        else:
+            return [r.cpu().numpy() if d0.numpy else r for r in rows]
+        return out.cpu().numpy() if d0.numpy else out
+
+    def _execute_items(self, d0, plans):
+        n = d0.n
+        start = _Pending(d0, d0.x, None, None)
+        start.members = list(range(n))
+        where = [(start, i) for i in range(n)]          # item -> (the _Pending batch that holds it, its row there)
+        pos = [0] * n
+        kept = [[] for _ in range(n)]                   # inputs of the parallel chains an item is inside of
+
+        def mat(pend):
+            if pend.mat is None:
+                pend.mat = pend.materialize()
+            return pend.mat
+
+        def row(i):
+            pend, r = where[i]
+            return mat(pend)[r]
+
+        def alone(i, t):
+            d = _Dev(t[None])
+            pend = _Pending(d, d.x, None, None)
+            pend.members = [i]
+            where[i] = (pend, 0)
+
+        while True:
+            for i in range(n):                          # the steps without a processor, item by item
+                while pos[i] < len(plans[i]) and plans[i][pos[i]][0] != "fx":
+                    op = plans[i][pos[i]]
+                    if op[0] == "begin":
+                        kept[i].append(row(i))
+                    else:
+                        w = op[1]
+                        alone(i, w * kept[i].pop() + (1 - w) * row(i))
+                    pos[i] += 1
+            groups = {}
+            for i in range(n):
+                if pos[i] < len(plans[i]):
+                    _, fx, _, rms, _ = plans[i][pos[i]]
+                    groups.setdefault((id(fx), rms, where[i][0].t.shape[2]), []).append(i)
+            if not groups:
+                break
+            # the processor most items wait for.  Any order is valid: an item's steps run in its own order and no item reads another's audio
+            items = max(groups.values(), key=len)
+            _, fx, _, rms, _ = plans[items[0]][pos[items[0]]]
+            pend = where[items[0]][0]
+            if not (all(where[i][0] is pend for i in items) and pend.members == items):
+                # the set changed: the pending factors are materialised and the rows gathered into a batch of their own
+                if all(where[i][0] is pend for i in items):
+                    t = mat(pend).index_select(0, torch.tensor([where[i][1] for i in items], device=pend.t.device))
+                else:
+                    t = torch.stack([row(i) for i in items], 0)
+                d = _Dev(t)
+                pend = _Pending(d, d.x, None, None)
+            out = self._apply_items(pend, fx, [plans[i][pos[i]][2] for i in items], rms, [plans[i][pos[i]][4] for i in items])
+            out.members = list(items)
+            for r, i in enumerate(items):
+                where[i] = (out, r)
+                pos[i] += 1
+        first = where[0][0]
+        if first.members == list(range(n)) and all(where[i][0] is first for i in range(n)):
+            return mat(first)
+        return [row(i) for i in range(n)]
 
     def __repr__(self):
         return f"AugmentationChain(fxs={self.fxs!r}, shuffle={self.shuffle!r})"
