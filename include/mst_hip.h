@@ -50,7 +50,7 @@ typedef enum {
 
 #define MST_MAX_BLOCKS 32
 
-int mst_version(void);          /* 103: per-item FX parameters, mst_fx_biquad_cascade_items / mst_fx_compressor_items / mst_fx_midside_imager_items / mst_fx_gain_items; 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
+int mst_version(void);          /* 104: mst_tcn_set_fusion / mst_tcn_get_fusion; 103: per-item FX parameters, mst_fx_biquad_cascade_items / mst_fx_compressor_items / mst_fx_midside_imager_items / mst_fx_gain_items; 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
 const char *mst_last_error(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -155,10 +155,24 @@ int mst_tcn_set_tuning(MstTcn *tcn, int flags);
  * either pointer may be null. */
 int mst_tcn_get_tuning(const MstTcn *tcn, int *flags, int *last_forward_fused_block0);
 
+/* Launch-level fusion of the handle (since mst_version() 104), beside the tuning flags: which KERNEL FORM a block runs stays what
+ * mst_tcn_set_tuning says; this decides whether blocks that qualify share a launch.  Same bits either way.
+ *   bit 0: the last three blocks of a full bf16 forward run as ONE launch (tcn_tail_bf16_kernel: the two activations between them stay in
+ *     LDS) when the net has at least four blocks and the three are planned as the whole-sequence 256-time forms of four, eight and sixteen
+ *     phases at dilations d, 2d, 4d with L = 64 d (tuning bit 7; d = 2048 / 4096 / 8192 at L = 131072).  Anything else - another length,
+ *     tuning without bit 7, mst_tcn_forward_blocks, another precision - runs one launch per block as before.
+ *   other bits: MST_ERR_ARG.
+ * A handle from mst_tcn_create starts with 0: its launch table is the one the tuning flags describe.  The Python modules set bit 0
+ * (_lib.TCN_FUSION_DEFAULT).  mst_tcn_get_fusion returns the flags and whether the handle's LAST forward ran the fused tail; either pointer
+ * may be null. */
+int mst_tcn_set_fusion(MstTcn *tcn, int flags);
+int mst_tcn_get_fusion(const MstTcn *tcn, int *flags, int *last_forward_fused_tail);
+
 /* measurement hook (bench.py's roofline leg): between _begin and _end every mst_tcn_forward records HIP events
  * on its stream around each kernel; _end synchronises, writes the AVERAGE milliseconds per forward of
  * block kernels 0..nblocks-1 followed by the output kernel into ms_out[nblocks+1], and the number of
- * forwards seen into *n_forwards. */
+ * forwards seen into *n_forwards.  A forward whose last three blocks ran as one launch (mst_tcn_set_fusion) reports that
+ * launch's time in three equal shares, one per block. */
 int mst_tcn_timing_begin(MstTcn *tcn, int max_forwards);
 int mst_tcn_timing_end(MstTcn *tcn, float *ms_out, int *n_forwards);
 

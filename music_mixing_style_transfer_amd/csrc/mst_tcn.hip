@@ -42,7 +42,10 @@ struct MstTcn {
     void *zero_row = nullptr;     // 1 KB of zeros: what the block kernels stage for time steps outside the segment
     int tuning = 245;             // TcnTuning flags (mst_tcn_set_tuning)
     int last_fused0 = 0;          // whether the last forward of this handle really ran block 0 inside block 1's launch (mst_tcn_get_tuning)
+    int fusion = 0;               // mst_tcn_set_fusion flags: launch-level, beside the tuning flags (a fresh handle's launch table is what the tuning flags say)
+    int last_fused_tail = 0;      // whether the last forward of this handle ran its last three blocks as one launch (mst_tcn_get_fusion)
     std::vector<hipEvent_t> ev;   // timing hook: (nblocks + 2) events per recorded forward
+    std::vector<char> ev_tail;    // per recorded forward: its last three blocks were one launch (their events coincide)
     int ev_max = 0, ev_used = 0;
 };
 
@@ -449,12 +452,28 @@ int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, i
                                  n == 1 && nblocks > 2 && t->d.dilations[0] == 1);
         if (plan[n].grid > 0x7fffffffL) return fail(MST_ERR_ARG, "mst_tcn_forward: grid too large");
     }
+    // the last three blocks as one launch (mst_tcn_set_fusion bit 0, tcn_tail_bf16_kernel): a full bf16 forward whose last three plans are exactly
+    // the whole-sequence 256-time forms of four, eight and sixteen phases at dilations d, 2d, 4d (L = 64 d) - their tiles are then the same
+    // samples.  Anything else (a step over or under in L, tuning without bit 7, a probe, another precision) runs the launches planned above.
+    bool tail = false;
+    if (precision == MST_PREC_BF16 && !act_out && n_run == nblocks && nblocks >= 4 && (t->fusion & 1)) {
+        const int n0 = nblocks - 3;
+        const int d0 = t->d.dilations[n0];
+        tail = t->d.dilations[n0 + 1] == 2 * d0 && t->d.dilations[n0 + 2] == 4 * d0;
+        for (int k = 0; k < 3; ++k) {
+            const TcnBlockPlan &p = plan[n0 + k];
+            tail = tail && p.family == TCN_BF16 && p.form == 1 && p.tile == 256 && p.P == (4 << k) && p.tiles_step == 1 && !p.block0 &&
+                   p.head == (k == 2) && p.grid == plan[n0].grid;
+        }
+    }
+    t->last_fused_tail = tail ? 1 : 0;
     const size_t buf_bytes = align_up((size_t)B * L * 128 * tcn_elem(precision), 256);
     unsigned char *buf[2] = {(unsigned char *)ws, (unsigned char *)ws + buf_bytes};
     const int Lp = L;
     hipEvent_t *ev = nullptr;
     if (!act_out && t->ev_used < t->ev_max) {
         ev = t->ev.data() + (size_t)t->ev_used * (nblocks + 2);
+        t->ev_tail[t->ev_used] = tail ? 1 : 0;
         t->ev_used++;
         MST_HIP_TRY(hipEventRecord(ev[0], (hipStream_t)stream));
     }
@@ -511,6 +530,24 @@ int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, i
             a.film0 = t->film;
             a.res0 = t->blk[0].res;
         }
+        if (tail && n == nblocks - 3) {
+            // one launch of the four-phase block's grid and tile order; the head's arguments are already in `a`
+            TcnTailArgs ta;
+            ta.a = a;
+            ta.a.y = nullptr;
+            ta.a.y_out = y;
+            for (int k = 0; k < 3; ++k) {
+                ta.wpk[k] = t->blk[n + k].w_bf16;
+                ta.shift[k] = t->blk[n + k].shift;
+                ta.film[k] = t->film + (size_t)(n + k) * t->film_rows * 256;
+                ta.res[k] = t->blk[n + k].res;
+            }
+            MST_LAUNCH(tcn_tail_bf16_kernel, dim3((unsigned)p.grid), dim3(256), stream, ta);
+            MST_CHECK_LAUNCH("tcn_tail_bf16_kernel");
+            if (ev)          // the three blocks' events coincide: mst_tcn_timing_end shares the launch's time among them
+                for (int k = 0; k < 3; ++k) MST_HIP_TRY(hipEventRecord(ev[n + k + 1], (hipStream_t)stream));
+            break;
+        }
         int rc;
         if ((rc = tcn_launch_block(p, a, stream))) return rc;
         if (ev) MST_HIP_TRY(hipEventRecord(ev[n + 1], (hipStream_t)stream));
@@ -566,11 +603,26 @@ extern "C" int mst_tcn_get_tuning(const MstTcn *t, int *flags, int *last_forward
     return MST_OK;
 }
 
+extern "C" int mst_tcn_set_fusion(MstTcn *t, int flags) {
+    if (!t) return fail(MST_ERR_ARG, "mst_tcn_set_fusion: null handle");
+    if (flags < 0 || flags > 1) return fail(MST_ERR_ARG, "mst_tcn_set_fusion: unknown flag bits (bit 0: the last three blocks as one launch)");
+    t->fusion = flags;
+    return MST_OK;
+}
+
+extern "C" int mst_tcn_get_fusion(const MstTcn *t, int *flags, int *last_forward_fused_tail) {
+    if (!t) return fail(MST_ERR_ARG, "mst_tcn_get_fusion: null handle");
+    if (flags) *flags = t->fusion;
+    if (last_forward_fused_tail) *last_forward_fused_tail = t->last_fused_tail;
+    return MST_OK;
+}
+
 extern "C" int mst_tcn_timing_begin(MstTcn *t, int max_forwards) {
     if (!t || max_forwards < 1) return fail(MST_ERR_ARG, "mst_tcn_timing_begin: bad argument");
     for (auto e : t->ev) (void)hipEventDestroy(e);
     t->ev.assign((size_t)max_forwards * (t->d.nblocks + 2), nullptr);
     for (auto &e : t->ev) MST_HIP_TRY(hipEventCreate(&e));
+    t->ev_tail.assign((size_t)max_forwards, 0);
     t->ev_max = max_forwards;
     t->ev_used = 0;
     return MST_OK;
@@ -582,11 +634,13 @@ extern "C" int mst_tcn_timing_end(MstTcn *t, float *ms_out, int *n_forwards) {
     for (int k = 0; k <= t->d.nblocks; ++k) ms_out[k] = 0.0f;
     for (int f = 0; f < t->ev_used; ++f) {
         MST_HIP_TRY(hipEventSynchronize(t->ev[(size_t)f * per + per - 1]));
-        for (int k = 0; k <= t->d.nblocks; ++k) {
-            float ms = 0.0f;
-            MST_HIP_TRY(hipEventElapsedTime(&ms, t->ev[(size_t)f * per + k], t->ev[(size_t)f * per + k + 1]));
-            ms_out[k] += ms;
+        float ms[MST_MAX_BLOCKS + 1] = {};
+        for (int k = 0; k <= t->d.nblocks; ++k) MST_HIP_TRY(hipEventElapsedTime(&ms[k], t->ev[(size_t)f * per + k], t->ev[(size_t)f * per + k + 1]));
+        if (t->ev_tail[f]) {      // the last three blocks were one launch: its time in equal shares
+            const int n0 = t->d.nblocks - 3;
+            ms[n0] = ms[n0 + 1] = ms[n0 + 2] = (ms[n0] + ms[n0 + 1] + ms[n0 + 2]) / 3.0f;
         }
+        for (int k = 0; k <= t->d.nblocks; ++k) ms_out[k] += ms[k];
     }
     if (t->ev_used > 0)
         for (int k = 0; k <= t->d.nblocks; ++k) ms_out[k] /= (float)t->ev_used;

@@ -592,6 +592,210 @@ __device__ __forceinline__ void tcn_reuse_class(f32x4 (&acc)[2][16], bf16x8 (&A0
 }
 
 // ------------------------------------------------------------------------------------------------
+// The LAST THREE blocks of a forward in one launch (mst_tcn_set_fusion bit 0; the host's conditions: tcn_run).  Where the three are the
+// whole-sequence 256-time forms <4 | 8 | 16, ., 8, 1> at dilations d, 2d, 4d (L = 64 d: d = 2048, 4096, 8192 at L = 131072) their tiles can be the
+// SAME set of samples: four residues mod d of one segment, as the flat row list
+//     row r = 4 s + phi  <->  time d s + 4 pg + phi                    s in [0, 64), phi in [0, 4)
+// which is the four-phase tile of the d block, an eight-phase tile of the 2d block (a step of 2d is 8 rows; its phases are the residues
+// 4 pg + phi and d + 4 pg + phi mod 2d) and a sixteen-phase tile of the 4d block (16 rows a step).  A dilated conv treats every residue
+// class alone, so any P residues are a tile; every input of every output of all three blocks is in the image, the rows beyond it are the
+// segment's zero padding: no halo is fetched and no MFMA computed twice.  The d block's epilogue leaves its bf16 tile in LDS where the 2d
+// block's main loop expects its input (row o + H P of the next form, the staging swizzle), and so on: the two activations between the three
+// blocks (2 x 1.07 GB written and read at 32 x 131072) never leave the CU, and neither do two staging passes, two store passes and two
+// launch seams.  Same main loops, tcn_epilogue4 and head as the three launches; an output's products and their summation order do not
+// depend on the column tile it sits in (all-padding pairs aside, which add zeros): bit-identical to the three launches.
+// Only __syncthreads() between the phases.  280 rows + three blocks' parameters = 76 KB of LDS: two workgroups per CU.
+// ------------------------------------------------------------------------------------------------
+struct TcnTailArgs {
+    TcnBlockArgs a;           // the d block's launch (its x, geometry with P = 4 and tiles_step = 1, tile order, zeros) and the head (out_w, out_b, y_out, nout); y is unused
+    const void *wpk[3];       // A fragments of the d, 2d and 4d blocks
+    const float *shift[3], *film[3], *res[3];      // their BN shifts, FiLM row bases (a.film_rows rows each) and residual scales
+};
+
+// the accumulators start from the BN shift of their channel
+__device__ __forceinline__ void tcn_tail_acc_init(f32x4 (&acc)[2][16], const float *par, int w, int g) {
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const f32x4 sh = *(const f32x4 *)(par + 32 * w + 16 * m + 4 * g);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[m][q] = sh;
+    }
+}
+
+// Epilogue of a block that is not the last: output o (input row o + ROW_IN of this form's image) -> row o + ROW_OUT, the next form's image,
+// in the swizzle of that row; ZERO_HALO: the next form keeps one halo step (8 rows) on either side of its 256 rows - padding, zeroed here.
+template <int ROW_IN, int ROW_OUT, bool ZERO_HALO>
+__device__ __forceinline__ void tcn_tail_hand_over(const f32x4 (&acc)[2][16], unsigned char *smem, const float *par, int tid) {
+    // lane coordinates from an OPAQUE copy of the thread index (like the row pass of tcn_block_bf16_kernel's epilogue): hipcc otherwise keeps
+    // this pass's addresses alive across the main loops - with three of them in one kernel that was a spill
+    asm volatile("" : "+v"(tid));
+    const int w = tid >> 6, l16 = tid & 15, g = (tid >> 4) & 3;
+    bf16x4 xin[2][16];
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const int co0 = 32 * w + 16 * m + 4 * g;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int row = 16 * q + l16 + ROW_IN;
+            xin[m][q] = *(const bf16x4 *)(smem + row * 256 + (((co0 >> 3) ^ (row & 15)) << 4) + 2 * (co0 & 7));
+        }
+    }
+    __syncthreads();          // every wave is through its main loop and has its residual rows: the image is dead
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const int co0 = 32 * w + 16 * m + 4 * g;
+        const f32x4 fr = *(const f32x4 *)(par + 128 + co0);
+        const f32x4 fb = *(const f32x4 *)(par + 256 + co0);
+        const f32x4 rs = *(const f32x4 *)(par + 384 + co0);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int row = 16 * q + l16 + ROW_OUT;
+            const float v4[4] = {acc[m][q][0], acc[m][q][1], acc[m][q][2], acc[m][q][3]};
+            *(bf16x4 *)(smem + row * 256 + (((co0 >> 3) ^ (row & 15)) << 4) + 2 * (co0 & 7)) = tcn_epilogue4(v4, fr, fb, rs, xin[m][q]);
+        }
+    }
+    if constexpr (ZERO_HALO) {
+        static_assert(!ZERO_HALO || ROW_OUT == 8, "rows [0, 8) and [264, 272): 16 rows, one 16-byte slot per thread");
+        const int r = tid >> 4;
+        const bf16x8 z = {};
+        *(bf16x8 *)(smem + (r < 8 ? r : 256 + r) * 256 + ((tid & 15) << 4)) = z;
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256, 2) void tcn_tail_bf16_kernel(TcnTailArgs ta) {
+    constexpr int T = 256, R = T + 2 * 3 * 4, NC = 16;          // the four-phase form's image: three halo steps either side
+    __shared__ __attribute__((aligned(16))) unsigned char smem[R * 256];
+    __shared__ __attribute__((aligned(16))) float par[3][4 * 128];      // per block: shift | FiLM r | FiLM b | res of this batch item
+    const TcnBlockArgs &a = ta.a;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int l16 = lane & 15, g = lane >> 4;
+
+    const int tile = a.xcd_tiles > 0 ? (int)(blockIdx.x & 7) * a.xcd_tiles + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int pg = tile % a.tiles_phase;          // (tiles_step = 1: a tile is its phases' whole sequence)
+    const int b = tile / a.tiles_phase;
+    const int phi0 = pg * 4;
+    // ---- stage the d block's 280 rows and the three blocks' parameters: tcn_block_bf16_kernel<4, false, 8, 1>'s staging pass
+    {
+        const __bf16 *xb = (const __bf16 *)a.x + (size_t)b * a.Lp * 128;
+        const int slot = tid & 15, prow = tid >> 4;
+        constexpr int NPASS = (R + 15) / 16;
+        const long dt = 4l * a.d;
+        long t = (long)(prow / 4 - 3) * a.d + phi0 + (prow % 4);
+        const __bf16 *src = xb + t * 128 + slot * 8;
+        const __bf16 *zsrc = (const __bf16 *)a.zeros + slot * 8;
+        bf16x8 v[NPASS];
+#pragma unroll
+        for (int i = 0; i < NPASS; ++i) {
+            const bool ok = prow + 16 * i < R && t >= 0 && t < a.L;          // never a predicated load (see there)
+            v[i] = *(const bf16x8 *)(ok ? src : zsrc);
+            t += dt;
+            src += dt * 128;
+        }
+        float pv[3][4];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int pc = tid & 127;
+            const float *frow0 = ta.film[k] + (a.film_rows > 1 ? (size_t)b * 256 : 0);
+            pv[k][0] = ta.shift[k][pc];
+            pv[k][1] = frow0[pc];
+            pv[k][2] = frow0[128 + pc];
+            pv[k][3] = ta.res[k][pc];
+        }
+        unsigned char *dst = smem + prow * 256 + ((slot ^ (prow & 15)) << 4);
+#pragma unroll
+        for (int i = 0; i < NPASS; ++i)
+            if (prow + 16 * i < R) *(bf16x8 *)(dst + i * 4096) = v[i];
+        if (tid < 128) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                par[k][tid] = pv[k][0];
+                par[k][128 + tid] = pv[k][1];
+                par[k][256 + tid] = pv[k][2];
+                par[k][384 + tid] = pv[k][3];
+            }
+        }
+    }
+    __syncthreads();
+
+    const unsigned aoff = (unsigned)(w * 64 + lane) * 16u;
+    f32x4 acc[2][NC];
+    // ---- the d block: four phases x 64 steps, outputs at rows 12 ...; its tile becomes the 2d block's image (one halo step: rows 8 ...)
+    tcn_tail_acc_init(acc, par[0], w, g);
+    tcn_class_major_whole_tile<4, NC, 3>(acc, smem, mst_stream16(ta.wpk[0], 60u * 2u * 4096u), aoff, l16, g);
+    tcn_tail_hand_over<12, 8, true>(acc, smem, par[0], (int)(aoff >> 4));
+    // ---- the 2d block: eight phases x 32 steps; its tile becomes the 4d block's image (no halo)
+    tcn_tail_acc_init(acc, par[1], w, g);
+    tcn_class_major_whole_tile<8, NC, 1>(acc, smem, mst_stream16(ta.wpk[1], 60u * 2u * 4096u), aoff, l16, g);
+    tcn_tail_hand_over<8, 0, false>(acc, smem, par[1], (int)(aoff >> 4));
+    // ---- the 4d block: sixteen phases x 16 steps, and the output head (tcn_block_bf16_kernel<16, true, 8, 1>'s epilogue)
+    tcn_tail_acc_init(acc, par[2], w, g);
+    tcn_class_major_whole_tile<16, NC, 0>(acc, smem, mst_stream16(ta.wpk[2], 60u * 2u * 4096u), aoff, l16, g);
+
+    // the thread index of the passes behind the main loops comes out of the weight stream's lane offset, which is live anyway (and opaque: see
+    // tcn_block_bf16_kernel's epilogue) - kept in a register of its own across three main loops it was the one that spilled
+    int tid_e = (int)(aoff >> 4);
+    asm volatile("" : "+v"(tid_e));
+    const int w_e = tid_e >> 6, l16_e = tid_e & 15, g_e = (tid_e >> 4) & 3;
+    bf16x4 xin[2][NC];
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const int co0 = 32 * w_e + 16 * m + 4 * g_e;
+#pragma unroll
+        for (int q = 0; q < NC; ++q) {
+            const int row = 16 * q + l16_e;
+            xin[m][q] = *(const bf16x4 *)(smem + row * 256 + (((co0 >> 3) ^ (row & 15)) << 4) + 2 * (co0 & 7));
+        }
+    }
+    __syncthreads();
+    float hs0[NC], hs1[NC];            // this lane's partial sums of the 1x1 output head, per column tile
+#pragma unroll
+    for (int q = 0; q < NC; ++q) hs0[q] = hs1[q] = 0.0f;
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const int co0 = 32 * w_e + 16 * m + 4 * g_e;
+        const f32x4 fr = *(const f32x4 *)(par[2] + 128 + co0);
+        const f32x4 fb = *(const f32x4 *)(par[2] + 256 + co0);
+        const f32x4 rs = *(const f32x4 *)(par[2] + 384 + co0);
+        f32x4 ow0 = *(const f32x4 *)(a.out_w + co0), ow1 = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (a.nout > 1) ow1 = *(const f32x4 *)(a.out_w + 128 + co0);
+#pragma unroll
+        for (int q = 0; q < NC; ++q) {
+            const float v4[4] = {acc[m][q][0], acc[m][q][1], acc[m][q][2], acc[m][q][3]};
+            const bf16x4 out = tcn_epilogue4(v4, fr, fb, rs, xin[m][q]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {          // the head reads the bf16-rounded activation
+                hs0[q] = fmaf(ow0[i], (float)out[i], hs0[q]);
+                hs1[q] = fmaf(ow1[i], (float)out[i], hs1[q]);
+            }
+        }
+    }
+    float *part = (float *)smem;                 // [4 waves][2 outputs][T columns]
+#pragma unroll
+    for (int q = 0; q < NC; ++q) {
+        hs0[q] += __shfl_xor(hs0[q], 16);
+        hs1[q] += __shfl_xor(hs1[q], 16);
+        hs0[q] += __shfl_xor(hs0[q], 32);
+        hs1[q] += __shfl_xor(hs1[q], 32);
+        if (g_e == 0) {
+            part[(w_e * 2 + 0) * T + 16 * q + l16_e] = hs0[q];
+            part[(w_e * 2 + 1) * T + 16 * q + l16_e] = hs1[q];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 2 * T / 256; ++i) {
+        const int idx = tid_e + 256 * i, c = idx / T, o = idx % T;
+        const long t = (long)(o / 4) * a.d + phi0 + (o % 4);          // the row list's time: the d block's four-phase order
+        if (c < a.nout && t < a.L) {
+            const float v = part[(0 * 2 + c) * T + o] + part[(1 * 2 + c) * T + o] + part[(2 * 2 + c) * T + o] +
+                            part[(3 * 2 + c) * T + o] + a.out_b[c];
+            a.y_out[((size_t)b * a.nout + c) * a.L + t] = fminf(1.0f, fmaxf(-1.0f, v));
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // blocks 1..n-1, "bf16x3" mode: fp32-class accuracy on the bf16 matrix cores.  Every fp32 operand is split
 //     x = x_hi + x_lo,  x_hi = bf16(x),  x_lo = bf16(x - x_hi)          (16 significant bits; products of two bf16 values are exact in fp32)
 // for the activations (while the tile is staged into LDS: two tiles, hi and lo) and for the BN-folded weights (on the host,

@@ -36,8 +36,46 @@ def timed(lib, tcn, x, cond, steps):
     return [float(v) for v in ms]
 
 
+def fusion_ab(lib, tcn, x, cond, args, out):
+    """--fusion: the last three blocks as one launch (mst_tcn_set_fusion 1) against the three launches it replaces (0), under the default
+    tuning flags: bit identity of y first, then the two alternating in this process - per pair the fused launch's time (mst_tcn_timing_end's
+    three equal shares, summed) against the sum of the three launches, and the whole forward's kernel time."""
+    from music_mixing_style_transfer_amd import _lib
+    nb = tcn.hparams.nblocks
+    lib.check(lib.mst_tcn_set_tuning(tcn._handle, _lib.TCN_TUNING_DEFAULT), "tuning")
+    ys, ran = {}, {}
+    for fu in (0, 1):
+        lib.check(lib.mst_tcn_set_fusion(tcn._handle, fu), "fusion")
+        ys[fu] = tcn(x, cond).clone()
+        torch.cuda.synchronize()
+        r = C.c_int(-1)
+        lib.check(lib.mst_tcn_get_fusion(tcn._handle, None, C.byref(r)), "get_fusion")
+        ran[fu] = r.value
+    same = bool(torch.equal(ys[0], ys[1]))
+    out["fusion"] = {"bit_identical": same, "tail_ran": ran, "pairs": []}
+    print(f"fusion 0 vs 1 at {args.batch}x2x{SEG}: bit identical {same}; fused tail ran {ran}", flush=True)
+    if not same or ran != {0: 0, 1: 1}:
+        sys.exit("the fused tail did not run or does not give the bits of the three launches: nothing timed")
+    for r in range(args.rounds):
+        pair = {}
+        for fu in (0, 1):
+            lib.check(lib.mst_tcn_set_fusion(tcn._handle, fu), "fusion")
+            ms = timed(lib, tcn, x, cond, args.steps)
+            pair[fu] = {"tail_ms": sum(ms[nb - 3:nb]), "forward_ms": sum(ms), "per_block_ms": ms}
+        out["fusion"]["pairs"].append(pair)
+        print(f"pair {r}: three launches {pair[0]['tail_ms']:.4f} ms, fused {pair[1]['tail_ms']:.4f} ms "
+              f"({pair[1]['tail_ms'] - pair[0]['tail_ms']:+.4f}); forward {pair[0]['forward_ms']:.4f} -> {pair[1]['forward_ms']:.4f} ms", flush=True)
+    lib.check(lib.mst_tcn_set_fusion(tcn._handle, _lib.TCN_FUSION_DEFAULT), "fusion")
+    if args.out:
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(out, fh, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fusion", action="store_true", help="A/B of mst_tcn_set_fusion 0 / 1 (the last three blocks as one launch) instead of the forms; "
+                                                         "use --rounds 5 or more")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
@@ -70,8 +108,8 @@ def main():
 
     # parity on a short segment against the oracle, every form
     xs, cs = synth.synth_audio((2, 2, 16384), seed=6), synth.synth_audio((1, tcn_cfg["condition_dimension"]), seed=7)
-    y_ref = R.tcn_forward(sd, xs, cs)
-    for f in forms:
+    y_ref = None if args.fusion else R.tcn_forward(sd, xs, cs)
+    for f in ([] if args.fusion else forms):
         lib.check(lib.mst_tcn_set_tuning(tcn._handle, f), "tuning")
         y = tcn(xs.to(dev), cs.to(dev)).cpu()
         out["forms"][str(f)] = {"max_abs_vs_oracle_16384": float((y - y_ref).abs().max())}
@@ -79,6 +117,9 @@ def main():
 
     x = synth.synth_audio((args.batch, 2, SEG), seed=200).to(dev)
     cond = synth.synth_audio((1, tcn_cfg["condition_dimension"]), seed=3).to(dev)
+    if args.fusion:
+        fusion_ab(lib, tcn, x, cond, args, out)
+        return
     ys = {}
     for f in forms:
         lib.check(lib.mst_tcn_set_tuning(tcn._handle, f), "tuning")
