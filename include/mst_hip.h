@@ -50,7 +50,7 @@ typedef enum {
 
 #define MST_MAX_BLOCKS 32
 
-int mst_version(void);          /* 104: mst_tcn_set_fusion / mst_tcn_get_fusion; 103: per-item FX parameters, mst_fx_biquad_cascade_items / mst_fx_compressor_items / mst_fx_midside_imager_items / mst_fx_gain_items; 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
+int mst_version(void);          /* 105: panner, Haas and both reverbs per item, mst_fx_panner_items / mst_fx_haas_items / mst_fx_convolve_items (+ its prepare, table and workspace queries) / mst_fx_algorithmic_reverb_items; 104: mst_tcn_set_fusion / mst_tcn_get_fusion; 103: per-item FX parameters, mst_fx_biquad_cascade_items / mst_fx_compressor_items / mst_fx_midside_imager_items / mst_fx_gain_items; 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
 const char *mst_last_error(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -463,6 +463,36 @@ void mst_fx_convolver_destroy(MstConvolver *cv);
 size_t mst_fx_convolver_workspace_bytes(const MstConvolver *cv);
 int mst_fx_convolve(MstConvolver *cv, const float *x_dev, const float *h_dev, long Lh, float *y_dev, long offset, double dry,
                     double wet, void *workspace_dev, size_t workspace_bytes, void *stream);
+/* PER-ITEM PARAMETERS, continued (since mst_version() 105): the panner, the Haas effect and both reverbs.  The conventions of the 103 entry
+ * points: parameters in device arrays, the item on the grid's y axis (n_items <= 65535), no global state, no synchronisation, nothing the
+ * caller's stream does not order.  Item i gets the bits of the shared-parameter call on the same batch with item i's settings: a per-item
+ * kernel runs the `__device__` body of its shared kernel with values read per item (the spectrum product repeats fx_conv_mul_kernel's).
+ * mst_fx_panner_items: gains_dev DEVICE float32 [n_items][2], the two gains of the pan law (computed by the caller, as for mst_fx_panner). */
+int mst_fx_panner_items(const float *x_dev, float *y_dev, int n_items, long L, int c_in, const float *gains_dev, void *stream);
+/* mst_fx_haas_items: delay_dev DEVICE int64 [n_items], of any sign and size - reduced on the device as mst_fx_haas does on the host, delay % L,
+ * + L if negative; feedback_dev DEVICE float64 [n_items], rounded to float32 as there; wet_channel_dev DEVICE int [n_items], 0 or 1 - any other
+ * value makes that item a plain copy of the stereo-expanded input (the reference's if / elif falls through).  In-place calls are refused. */
+int mst_fx_haas_items(const float *x_dev, float *y_dev, int n_items, long L, int c_in, const long *delay_dev, const double *feedback_dev,
+                      const int *wet_channel_dev, void *stream);
+/* mst_fx_convolve with an impulse response, an offset, dry and wet PER ITEM, on an existing convolver: its L, Lh_max, C and item capacity fix
+ * the transform size and the overlap-save geometry, so item i has the bits of mst_fx_convolve on that convolver with item i's response and
+ * settings.  bank_dev: DEVICE float32 [bank_frames][C], the n_resp DISTINCT responses of the batch back to back in the audio layout; several
+ * items may name the same response, which is packed and transformed once per call.  An item whose wet is 0 is its input exactly, whatever dry
+ * is (ConvolutionalReverb.process returns x).
+ * mst_fx_convolve_items_prepare (host only, launches nothing) checks and fills the table the call reads - table_host, of
+ * mst_fx_convolve_items_table_bytes(n_items, n_resp), meant to be pinned and uploaded without waiting - from resp_start_host / resp_len_host
+ * [n_resp] (first frame and frames of each response in the bank) and params_host [n_items][4] = response index, offset, dry, wet.  Refused:
+ * a response with len outside 1 ... Lh_max or start + len > bank_frames (MST_ERR_ARG, the message names the response, first_bad_item -1); an
+ * item whose response index is outside [0, n_resp) or whose offset is outside [0, len - 1] (MST_ERR_ARG, the message names the item, its index
+ * in first_bad_item); n_items beyond the convolver's capacity (MST_ERR_ARG, first_bad_item = the capacity, the first item without a place);
+ * (n_items * blocks per sequence + n_resp) * C > 65535 (MST_ERR_UNSUPPORTED: split the batch).  workspace: caller memory of
+ * mst_fx_convolver_items_workspace_bytes(cv, n_resp), else MST_ERR_WORKSPACE. */
+size_t mst_fx_convolver_items_workspace_bytes(const MstConvolver *cv, int n_resp);
+size_t mst_fx_convolve_items_table_bytes(int n_items, int n_resp);
+int mst_fx_convolve_items_prepare(const MstConvolver *cv, const long *resp_start_host, const long *resp_len_host, int n_resp, long bank_frames,
+                                  const double *params_host, int n_items, double *table_host, size_t table_bytes, int *first_bad_item);
+int mst_fx_convolve_items(MstConvolver *cv, const float *x_dev, const float *bank_dev, const double *table_dev, int n_items, int n_resp,
+                          float *y_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 /* Gain.process (:1041-1051) */
 int mst_fx_gain(const float *x_dev, float *y_dev, int n_items, long L, int C, double gain_db, int invert, const MstFxFuse *fuse,
                 void *stream);
@@ -527,6 +557,13 @@ int mst_fx_algorithmic_reverb(const float *x_dev, float *y_dev, int n_items, lon
                               const int *allpass_delays, int n_allpass, int stereo_spread, double damping, double room_size,
                               double in_gain, double wet1, double wet2, double dry, double *scratch_dev, size_t scratch_bytes,
                               void *stream);
+
+/* mst_fx_algorithmic_reverb with damping, room_size, wet1, wet2 and dry PER ITEM (since mst_version() 105): params_dev DEVICE float64
+ * [n_items][5] in that order; in_gain, the delays and stereo_spread stay shared (class constants of the processor).  Scratch as for the shared
+ * call, whose bits item i gets for its row; n_items <= 32767 (two sides per item on a grid axis). */
+int mst_fx_algorithmic_reverb_items(const float *x_dev, float *y_dev, int n_items, long L, int C, const int *comb_delays, int n_combs,
+                                    const int *allpass_delays, int n_allpass, int stereo_spread, double in_gain, const double *params_dev,
+                                    double *scratch_dev, size_t scratch_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Multi-scale spectral distance: MultiScale_Spectral_Loss_MidSide_DDSP (modules/loss.py:99-213) over FrontEnd(mode=["mag"])

@@ -198,6 +198,14 @@ SIGNATURES = {
     "mst_resample_length": (C.c_long, [_P, C.c_long]),
     "mst_resample_taps": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int]),
     "mst_resample_forward": (C.c_int, [_P, _F, C.c_long, C.c_long, _F, C.c_long, C.c_long, C.c_int, C.c_int, _P]),
+    "mst_fx_panner_items": (C.c_int, [_F, _F, C.c_int, C.c_long, C.c_int, _P, _P]),
+    "mst_fx_haas_items": (C.c_int, [_F, _F, C.c_int, C.c_long, C.c_int, _P, _P, _P, _P]),
+    "mst_fx_convolver_items_workspace_bytes": (C.c_size_t, [_P, C.c_int]),
+    "mst_fx_convolve_items_table_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "mst_fx_convolve_items_prepare": (C.c_int, [_P, _P, _P, C.c_int, C.c_long, _P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_int)]),
+    "mst_fx_convolve_items": (C.c_int, [_P, _F, _F, _P, C.c_int, C.c_int, _F, _P, C.c_size_t, _P]),
+    "mst_fx_algorithmic_reverb_items": (C.c_int, [_F, _F, C.c_int, C.c_long, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int,
+                                                  C.c_int, C.c_double, _P, _P, C.c_size_t, _P]),
     "mst_fx_convolve": (C.c_int, [_P, _F, _F, C.c_long, _F, C.c_long, C.c_double, C.c_double, _P, C.c_size_t, _P]),
 }
 

@@ -1443,7 +1443,7 @@ __host__ __device__ __forceinline__ float fx_gain_factor(double gain_db, int inv
 // Haas effect, haas_process (:768-786): y = x; y[:, ch] += feedback * np.roll(x[:, ch], delay).  np.roll is circular:
 // roll(x, d)[i] = x[(i - d) mod L]; `shift` = delay mod L in [0, L).  float32 like numpy on a float32 array: one
 // rounded multiply, one rounded add (no fused multiply-add).  A mono input [L, 1] is repeated to stereo first (:838-839).
-__global__ __launch_bounds__(256) void fx_haas_kernel(const float *x, float *y, long L, int c_in, long shift, float fb, int ch) {
+__device__ __forceinline__ void fxb_haas(const float *x, float *y, long L, int c_in, long shift, float fb, int ch) {
     const int item = blockIdx.y;
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= L) return;
@@ -1459,9 +1459,30 @@ __global__ __launch_bounds__(256) void fx_haas_kernel(const float *x, float *y, 
     yp[0] = l;
     yp[1] = r;
 }
+__global__ __launch_bounds__(256) void fx_haas_kernel(const float *x, float *y, long L, int c_in, long shift, float fb, int ch) {
+    fxb_haas(x, y, L, c_in, shift, fb, ch);
+}
+// per item (mst_fx_haas_items): the delay reduced modulo L as mst_fx_haas does on the host, the feedback rounded to float32 as there; a wet
+// channel other than 0 / 1 leaves the stereo-expanded input (the reference's if / elif falls through, :782-785)
+__global__ __launch_bounds__(256) void fxsi_haas_kernel(const float *x, float *y, long L, int c_in, const long *__restrict__ delay,
+                                                        const double *__restrict__ feedback, const int *__restrict__ wet_channel) {
+    const int item = blockIdx.y, ch = wet_channel[item];
+    if (ch != 0 && ch != 1) {
+        const long i = (long)blockIdx.x * 256 + threadIdx.x;
+        if (i >= L) return;
+        const float *xp = x + ((size_t)item * L + i) * c_in;
+        float *yp = y + ((size_t)item * L + i) * 2;
+        yp[0] = xp[0];
+        yp[1] = xp[c_in - 1];
+        return;
+    }
+    long shift = delay[item] % L;
+    if (shift < 0) shift += L;
+    fxb_haas(x, y, L, c_in, shift, (float)feedback[item], ch);
+}
 
 // Panner.process (:927-943): x * gains, mono repeated to stereo first; the gains come from the pan law on the host
-__global__ __launch_bounds__(256) void fx_panner_kernel(const float *x, float *y, long L, int c_in, float g0, float g1) {
+__device__ __forceinline__ void fxb_panner(const float *x, float *y, long L, int c_in, float g0, float g1) {
     const int item = blockIdx.y;
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= L) return;
@@ -1469,6 +1490,13 @@ __global__ __launch_bounds__(256) void fx_panner_kernel(const float *x, float *y
     float *yp = y + ((size_t)item * L + i) * 2;
     yp[0] = xp[0] * g0;
     yp[1] = xp[c_in - 1] * g1;
+}
+__global__ __launch_bounds__(256) void fx_panner_kernel(const float *x, float *y, long L, int c_in, float g0, float g1) {
+    fxb_panner(x, y, L, c_in, g0, g1);
+}
+// per item (mst_fx_panner_items): gains [n_items][2], the pan law evaluated on the host
+__global__ __launch_bounds__(256) void fxsi_panner_kernel(const float *x, float *y, long L, int c_in, const float *__restrict__ gains) {
+    fxb_panner(x, y, L, c_in, gains[2 * blockIdx.y], gains[2 * blockIdx.y + 1]);
 }
 
 // ---- FFT convolution (ConvolutionalReverb.process, common_audioeffects.py:727-764; the normaliser's 1001-tap FIR) ----------------
@@ -1495,8 +1523,8 @@ __global__ __launch_bounds__(256) void fx_conv_mul_kernel(float2 *X, const float
 }
 
 // y[item][t][c] = dry * x[item][t][c] + wet * conv[item, c][offset + t]   (the reference cuts y[idx : idx + len(x)], :754-761)
-__global__ __launch_bounds__(256) void fx_conv_mix_kernel(const float *x, const float *seq, float *y, long L, int C, long n_fft, int nb,
-                                                          long step, long shift, long offset, float dry, float wet) {
+__device__ __forceinline__ void fxb_conv_mix(const float *x, const float *seq, float *y, long L, int C, long n_fft, int nb, long step,
+                                             long shift, long offset, float dry, float wet) {
     const int item = blockIdx.y;
     const long e = (long)blockIdx.x * 256 + threadIdx.x;          // element of the [L][C] item
     if (e >= L * C) return;
@@ -1504,6 +1532,42 @@ __global__ __launch_bounds__(256) void fx_conv_mix_kernel(const float *x, const 
     const int c = (int)(e % C);
     const float v = seq[(((size_t)item * C + c) * nb + b) * n_fft + shift + (m - b * step)];
     y[(size_t)item * L * C + e] = dry * x[(size_t)item * L * C + e] + wet * v;
+}
+__global__ __launch_bounds__(256) void fx_conv_mix_kernel(const float *x, const float *seq, float *y, long L, int C, long n_fft, int nb,
+                                                          long step, long shift, long offset, float dry, float wet) {
+    fxb_conv_mix(x, seq, y, L, C, n_fft, nb, step, shift, offset, dry, wet);
+}
+
+// ---- a response per item (mst_fx_convolve_items).  The table mst_fx_convolve_items_prepare fills, float64: [n_resp][2] = first frame and
+// length of each response inside the bank, then [n_items][5] = response index, offset, dry, wet, copy flag (wet == 0: the item is its input).
+#define MST_CONV_ITEM_FIELDS 5
+// pack: the ragged bank [bank_frames][C] -> n_resp * C zero-padded real sequences of n_fft samples (what fx_conv_pack_kernel makes of one response)
+__global__ __launch_bounds__(256) void fxsi_conv_pack_bank_kernel(const float *bank, float *seq, const double *__restrict__ table, int C, long n_fft) {
+    const int blk = blockIdx.y, r = blk / C, c = blk % C;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_fft) return;
+    const long start = (long)table[2 * r], len = (long)table[2 * r + 1];
+    seq[(size_t)blk * n_fft + i] = i < len ? bank[(size_t)(start + i) * C + c] : 0.0f;
+}
+// fx_conv_mul_kernel with H[resp(item)][c]; items: the [n_items][5] part of the table.  (That kernel keeps its text: as a caller of a shared
+// body it compiled to another scalar-register count.  The product is repeated here term for term and held to its bits by the tests.)
+__global__ __launch_bounds__(256) void fxsi_conv_mul_kernel(float2 *X, const float2 *H, const double *__restrict__ items, long nbin, int C, int nb, float scale) {
+    const int blk = blockIdx.y, sq = blk / nb, item = sq / C;
+    const long k = (long)blockIdx.x * 256 + threadIdx.x;
+    if (k >= nbin) return;
+    const int r = (int)items[(size_t)item * MST_CONV_ITEM_FIELDS];
+    const float2 a = X[(size_t)blk * nbin + k], b = H[((size_t)r * C + sq % C) * nbin + k];
+    X[(size_t)blk * nbin + k] = make_float2((a.x * b.x - a.y * b.y) * scale, (a.x * b.y + a.y * b.x) * scale);
+}
+__global__ __launch_bounds__(256) void fxsi_conv_mix_kernel(const float *x, const float *seq, float *y, const double *__restrict__ items, long L, int C,
+                                                            long n_fft, int nb, long step, long shift) {
+    const double *it = items + (size_t)blockIdx.y * MST_CONV_ITEM_FIELDS;
+    if (it[4] != 0.0) {          // wet == 0: ConvolutionalReverb.process returns x
+        const long e = (long)blockIdx.x * 256 + threadIdx.x;
+        if (e < L * C) y[(size_t)blockIdx.y * L * C + e] = x[(size_t)blockIdx.y * L * C + e];
+        return;
+    }
+    fxb_conv_mix(x, seq, y, L, C, n_fft, nb, step, shift, (long)it[1], (float)it[2], (float)it[3]);
 }
 
 // =================================================================================================
@@ -1701,7 +1765,7 @@ struct CombArgs {
 };
 
 // grid (n_combs, n_items * 2), 64 threads: one wave per (comb, item, side)
-__global__ __launch_bounds__(64) void fx_comb_kernel(CombArgs a) {
+__device__ __forceinline__ void fxb_comb(const CombArgs &a, const double damp, const double feedback) {
     constexpr int EMAX = 32;                                    // delay <= 64 * EMAX = 2048 samples
     __shared__ double store_prev[64 * EMAX];                    // store values of the previous block
     const int comb = blockIdx.x, sq = blockIdx.y, item = sq >> 1, side = sq & 1, lane = threadIdx.x;
@@ -1711,7 +1775,7 @@ __global__ __launch_bounds__(64) void fx_comb_kernel(CombArgs a) {
     const int cnt = D - i0 < 0 ? 0 : (D - i0 < E ? D - i0 : E); // this lane's share of the D samples of a block
     const float *xp = a.x + (size_t)item * a.L * a.C + (a.C == 2 ? side : 0);
     double *yp = a.y + ((size_t)comb * a.n_items * 2 + sq) * a.L;
-    const double d1 = a.damp, d2 = 1.0 - a.damp;
+    const double d1 = damp, d2 = 1.0 - damp;
     double dC = 1.0;                                            // damp^cnt: the decay a carry suffers across this lane's run
     for (int i = 0; i < cnt; ++i) dC *= d1;
     double carry_in = 0.0;                                      // store value just before the block
@@ -1723,7 +1787,7 @@ __global__ __launch_bounds__(64) void fx_comb_kernel(CombArgs a) {
             double o = 0.0;
             if (e < cnt) {
                 const long n = n0 + i0 + e;
-                if (n0 > 0 && n < a.L) o = (double)xp[(n - D) * a.C] * a.in_gain + store_prev[i0 + e] * a.feedback;
+                if (n0 > 0 && n < a.L) o = (double)xp[(n - D) * a.C] * a.in_gain + store_prev[i0 + e] * feedback;
                 s = d1 * s + d2 * o;                            // the run from a zero carry
             }
             out[e] = o;
@@ -1756,10 +1820,20 @@ __global__ __launch_bounds__(64) void fx_comb_kernel(CombArgs a) {
     }
 }
 
+__global__ __launch_bounds__(64) void fx_comb_kernel(CombArgs a) {
+    fxb_comb(a, a.damp, a.feedback);
+}
+// per item (mst_fx_algorithmic_reverb_items): params [n_items][5] = damping, room_size, wet1, wet2, dry
+#define MST_REVERB_ITEM_FIELDS 5
+__global__ __launch_bounds__(64) void fxsi_comb_kernel(CombArgs a, const double *__restrict__ params) {
+    const double *p = params + (size_t)(blockIdx.y >> 1) * MST_REVERB_ITEM_FIELDS;
+    fxb_comb(a, p[0], p[1]);
+}
+
 // one all-pass section in place over v[sq][L]: thread p of a workgroup owns the samples n = p, p + D, p + 2D, ...;
 // sum_combs > 0: the input is first formed as the sum of that many comb outputs (y layout of fx_comb_kernel)
-__global__ __launch_bounds__(1024) void fx_allpass_kernel(double *v, const double *combs, int sum_combs, int first_comb, long L, int n_seq,
-                                                          int delay_l, int delay_r, double feedback) {
+__device__ __forceinline__ void fxb_allpass(double *v, const double *combs, int sum_combs, int first_comb, long L, int n_seq,
+                                            int delay_l, int delay_r, double feedback) {
     const int sq = blockIdx.x, side = sq & 1;
     const int D = side ? delay_r : delay_l;
     double *vp = v + (size_t)sq * L;
@@ -1777,10 +1851,17 @@ __global__ __launch_bounds__(1024) void fx_allpass_kernel(double *v, const doubl
         }
     }
 }
+__global__ __launch_bounds__(1024) void fx_allpass_kernel(double *v, const double *combs, int sum_combs, int first_comb, long L, int n_seq,
+                                                          int delay_l, int delay_r, double feedback) {
+    fxb_allpass(v, combs, sum_combs, first_comb, L, n_seq, delay_l, delay_r, feedback);
+}
+__global__ __launch_bounds__(1024) void fxsi_allpass_kernel(double *v, const double *combs, int sum_combs, int first_comb, long L, int n_seq,
+                                                            int delay_l, int delay_r, const double *__restrict__ params) {
+    fxb_allpass(v, combs, sum_combs, first_comb, L, n_seq, delay_l, delay_r, params[(size_t)(blockIdx.x >> 1) * MST_REVERB_ITEM_FIELDS + 1]);
+}
 
 // output[:, 0] = wet1 xL + wet2 xR + dry dataL ; output[:, 1] = wet1 xR + wet2 xL + dry dataR  (:1462-1463)
-__global__ __launch_bounds__(256) void fx_reverb_mix_kernel(const float *x, const double *wet, float *y, long L, int C, double wet1, double wet2,
-                                                            double dry) {
+__device__ __forceinline__ void fxb_reverb_mix(const float *x, const double *wet, float *y, long L, int C, double wet1, double wet2, double dry) {
     const int item = blockIdx.y;
     const long n = (long)blockIdx.x * 256 + threadIdx.x;
     if (n >= L) return;
@@ -1790,6 +1871,14 @@ __global__ __launch_bounds__(256) void fx_reverb_mix_kernel(const float *x, cons
     float *yp = y + ((size_t)item * L + n) * 2;
     yp[0] = (float)(wet1 * xl + wet2 * xr + dry * dl);
     yp[1] = (float)(wet1 * xr + wet2 * xl + dry * dr);
+}
+__global__ __launch_bounds__(256) void fx_reverb_mix_kernel(const float *x, const double *wet, float *y, long L, int C, double wet1, double wet2,
+                                                            double dry) {
+    fxb_reverb_mix(x, wet, y, L, C, wet1, wet2, dry);
+}
+__global__ __launch_bounds__(256) void fxsi_reverb_mix_kernel(const float *x, const double *wet, float *y, long L, int C, const double *__restrict__ params) {
+    const double *p = params + (size_t)blockIdx.y * MST_REVERB_ITEM_FIELDS;
+    fxb_reverb_mix(x, wet, y, L, C, p[2], p[3], p[4]);
 }
 
 // chain fusion: the pending factor of an rms-normalise step (apply_processor :143-146) from the sums the producers left behind:

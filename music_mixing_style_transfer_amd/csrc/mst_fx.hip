@@ -1047,6 +1047,27 @@ extern "C" int mst_fx_panner(const float *x, float *y, int n_items, long L, int 
     return MST_OK;
 }
 
+extern "C" int mst_fx_panner_items(const float *x, float *y, int n_items, long L, int c_in, const float *gains_dev, void *stream) {
+    if (!x || !y || !gains_dev || n_items < 1 || n_items > 65535 || L < 1) return fail(MST_ERR_ARG, "mst_fx_panner_items: bad argument");
+    if (c_in != 1 && c_in != 2) return fail(MST_ERR_ARG, "mst_fx_panner_items: Panner only works with monaural or stereo audio");
+    if (x == y && c_in != 2) return fail(MST_ERR_ARG, "mst_fx_panner_items: in-place needs a stereo input");
+    MST_LAUNCH(fxsi_panner_kernel, dim3((unsigned)((L + 255) / 256), n_items), dim3(256), stream, x, y, L, c_in, gains_dev);
+    MST_CHECK_LAUNCH("fxsi_panner_kernel");
+    return MST_OK;
+}
+
+extern "C" int mst_fx_haas_items(const float *x, float *y, int n_items, long L, int c_in, const long *delay_dev, const double *feedback_dev,
+                                 const int *wet_channel_dev, void *stream) {
+    if (!x || !y || !delay_dev || !feedback_dev || !wet_channel_dev || n_items < 1 || n_items > 65535 || L < 1)
+        return fail(MST_ERR_ARG, "mst_fx_haas_items: bad argument");
+    if (c_in != 1 && c_in != 2) return fail(MST_ERR_ARG, "mst_fx_haas_items: Haas effect only works with monaural or stereo audio");
+    if (x == y) return fail(MST_ERR_ARG, "mst_fx_haas_items: in-place operation is not supported (circular read)");
+    MST_LAUNCH(fxsi_haas_kernel, dim3((unsigned)((L + 255) / 256), n_items), dim3(256), stream, x, y, L, c_in, delay_dev, feedback_dev,
+               wet_channel_dev);
+    MST_CHECK_LAUNCH("fxsi_haas_kernel");
+    return MST_OK;
+}
+
 // ---- power-of-two real FFTs (csrc/fft_kernels.h): plans for the FFT convolution and the STFT ---------------------------------------
 struct MstFftPlan {
     long n = 0, m = 0;              // transform length, m = n / 2 complex points
@@ -1250,6 +1271,100 @@ extern "C" int mst_fx_convolve(MstConvolver *cv, const float *x, const float *h,
     return MST_OK;
 }
 
+// ---- a response per item: the responses of a batch back to back in one bank, each packed and transformed once ------------------------
+extern "C" size_t mst_fx_convolver_items_workspace_bytes(const MstConvolver *cv, int n_resp) {
+    if (!cv || n_resp < 1) return 0;
+    const size_t nbin = (size_t)cv->n_fft / 2 + 1, seqs = (size_t)cv->n_items * cv->C * cv->nb + (size_t)n_resp * cv->C;
+    return seqs * (size_t)cv->n_fft * sizeof(float) + seqs * nbin * sizeof(float2) + 256;
+}
+
+extern "C" size_t mst_fx_convolve_items_table_bytes(int n_items, int n_resp) {
+    if (n_items < 1 || n_resp < 1) return 0;
+    return ((size_t)n_resp * 2 + (size_t)n_items * MST_CONV_ITEM_FIELDS) * sizeof(double);
+}
+
+extern "C" int mst_fx_convolve_items_prepare(const MstConvolver *cv, const long *resp_start_host, const long *resp_len_host, int n_resp,
+                                             long bank_frames, const double *params_host, int n_items, double *table_host,
+                                             size_t table_bytes, int *first_bad_item) {
+    if (first_bad_item) *first_bad_item = -1;
+    if (!cv || !resp_start_host || !resp_len_host || !params_host || !table_host || n_resp < 1 || n_items < 1 || bank_frames < 1)
+        return fail(MST_ERR_ARG, "mst_fx_convolve_items_prepare: bad argument");
+    if (table_bytes < mst_fx_convolve_items_table_bytes(n_items, n_resp)) return fail(MST_ERR_WORKSPACE, "mst_fx_convolve_items_prepare: table too small");
+    char buf[200];
+    if (n_items > cv->n_items) {
+        if (first_bad_item) *first_bad_item = cv->n_items;
+        std::snprintf(buf, sizeof(buf), "mst_fx_convolve_items_prepare: item %d: the convolver was created for %d items", cv->n_items, cv->n_items);
+        return fail(MST_ERR_ARG, buf);
+    }
+    if (((long)n_items * cv->nb + n_resp) * cv->C > 65535)
+        return fail(MST_ERR_UNSUPPORTED, "mst_fx_convolve_items_prepare: more than 65535 transform blocks (split the batch)");
+    for (int r = 0; r < n_resp; ++r) {
+        const long start = resp_start_host[r], len = resp_len_host[r];
+        if (len < 1 || len > cv->Lh_max) {
+            std::snprintf(buf, sizeof(buf), "mst_fx_convolve_items_prepare: response %d: %ld frames, the convolver takes 1 ... %ld", r, len, cv->Lh_max);
+            return fail(MST_ERR_ARG, buf);
+        }
+        if (start < 0 || start > bank_frames - len) {
+            std::snprintf(buf, sizeof(buf), "mst_fx_convolve_items_prepare: response %d: frames %ld ... %ld lie outside the bank of %ld", r, start, start + len, bank_frames);
+            return fail(MST_ERR_ARG, buf);
+        }
+        table_host[2 * r] = (double)start;
+        table_host[2 * r + 1] = (double)len;
+    }
+    double *items = table_host + 2 * (size_t)n_resp;
+    for (int i = 0; i < n_items; ++i) {
+        const double *p = params_host + 4 * (size_t)i;
+        double *t = items + (size_t)i * MST_CONV_ITEM_FIELDS;
+        if (!(p[0] >= 0 && p[0] < n_resp) || p[0] != std::floor(p[0])) {
+            if (first_bad_item) *first_bad_item = i;
+            std::snprintf(buf, sizeof(buf), "mst_fx_convolve_items_prepare: item %d: response index %g outside [0, %d)", i, p[0], n_resp);
+            return fail(MST_ERR_ARG, buf);
+        }
+        const long len = resp_len_host[(int)p[0]];
+        if (!(p[1] >= 0 && p[1] <= (double)(len - 1)) || p[1] != std::floor(p[1])) {
+            if (first_bad_item) *first_bad_item = i;
+            std::snprintf(buf, sizeof(buf), "mst_fx_convolve_items_prepare: item %d: offset %g outside [0, Lh-1] of its response of %ld frames", i, p[1], len);
+            return fail(MST_ERR_ARG, buf);
+        }
+        t[0] = p[0];
+        t[1] = p[1];
+        t[2] = p[2];
+        t[3] = p[3];
+        t[4] = p[3] == 0.0 ? 1.0 : 0.0;          // ConvolutionalReverb.process returns x when wet == 0
+    }
+    return MST_OK;
+}
+
+extern "C" int mst_fx_convolve_items(MstConvolver *cv, const float *x, const float *bank, const double *table_dev, int n_items, int n_resp,
+                                     float *y, void *ws, size_t ws_bytes, void *stream) {
+    if (!cv || !x || !bank || !table_dev || !y || !ws || n_items < 1 || n_resp < 1) return fail(MST_ERR_ARG, "mst_fx_convolve_items: bad argument");
+    if (n_items > cv->n_items) return fail(MST_ERR_ARG, "mst_fx_convolve_items: more items than the convolver was created for");
+    if (((long)n_items * cv->nb + n_resp) * cv->C > 65535) return fail(MST_ERR_UNSUPPORTED, "mst_fx_convolve_items: more than 65535 transform blocks (split the batch)");
+    if (ws_bytes < mst_fx_convolver_items_workspace_bytes(cv, n_resp)) return fail(MST_ERR_WORKSPACE, "mst_fx_convolve_items: workspace too small");
+    const long n = cv->n_fft, nbin = n / 2 + 1;
+    const int C = cv->C, nb = cv->nb, nblk = n_items * C * nb, nh = n_resp * C;
+    int rc;
+    // the layout of mst_fx_convolve with the convolver's full item capacity in front of the responses
+    float *rx = (float *)ws, *rh = rx + (size_t)cv->n_items * C * nb * n;
+    float2 *cx = (float2 *)(((uintptr_t)(rh + (size_t)nh * n) + 255) & ~(uintptr_t)255), *ch = cx + (size_t)cv->n_items * C * nb * nbin;
+    const double *items = table_dev + 2 * (size_t)n_resp;
+    const unsigned gb = (unsigned)((n + 255) / 256);
+    MST_LAUNCH(fx_conv_pack_kernel, dim3(gb, nblk), dim3(256), stream, x, rx, cv->L, C, n, nb, cv->step, cv->shift);
+    MST_CHECK_LAUNCH("fx_conv_pack_kernel");
+    MST_LAUNCH(fxsi_conv_pack_bank_kernel, dim3(gb, nh), dim3(256), stream, bank, rh, table_dev, C, n);
+    MST_CHECK_LAUNCH("fxsi_conv_pack_bank_kernel");
+    if ((rc = fft_exec_r2c(cv->plan, rx, cx, nblk, stream)) || (rc = fft_exec_r2c(cv->plan, rh, ch, nh, stream))) return rc;
+    MST_LAUNCH(fxsi_conv_mul_kernel, dim3((unsigned)((nbin + 255) / 256), nblk), dim3(256), stream, cx, (const float2 *)ch, items, nbin, C, nb,
+               1.0f / (float)n);
+    MST_CHECK_LAUNCH("fxsi_conv_mul_kernel");
+    if ((rc = fft_exec_c2r(cv->plan, cx, rx, nblk, stream))) return rc;
+    const long per = cv->L * C;
+    MST_LAUNCH(fxsi_conv_mix_kernel, dim3((unsigned)((per + 255) / 256), n_items), dim3(256), stream, x, (const float *)rx, y, items, cv->L, C, n,
+               nb, cv->step, cv->shift);
+    MST_CHECK_LAUNCH("fxsi_conv_mix_kernel");
+    return MST_OK;
+}
+
 extern "C" int mst_fx_rms_normalize(const float *x, float *y, int n_items, long per_x, long per_y, double *scratch, void *stream) {
     if (!x || !y || !scratch || n_items < 1 || per_x < 1 || per_y < 1) return fail(MST_ERR_ARG, "mst_fx_rms_normalize: bad argument");
     int rc;
@@ -1375,15 +1490,17 @@ extern "C" size_t mst_fx_algorithmic_reverb_scratch_bytes(int n_items, long L, i
     return ((size_t)n_combs + 1) * n_items * 2 * (size_t)L * sizeof(double);
 }
 
-extern "C" int mst_fx_algorithmic_reverb(const float *x, float *y, int n_items, long L, int C, const int *comb_delays, int n_combs,
-                                         const int *allpass_delays, int n_allpass, int stereo_spread, double damping, double room_size,
-                                         double in_gain, double wet1, double wet2, double dry, double *scratch, size_t scratch_bytes,
-                                         void *stream) {
+namespace {
+// params_dev == NULL: the shared call with its five scalars; else DEVICE [n_items][5] = damping, room_size, wet1, wet2, dry read per item
+int reverb_run(const char *who, const float *x, float *y, int n_items, long L, int C, const int *comb_delays, int n_combs,
+               const int *allpass_delays, int n_allpass, int stereo_spread, double damping, double room_size, double in_gain, double wet1,
+               double wet2, double dry, const double *params_dev, double *scratch, size_t scratch_bytes, void *stream) {
+    const std::string name(who);
     if (!x || !y || !comb_delays || !allpass_delays || !scratch || n_items < 1 || L < 1 || (C != 1 && C != 2) || n_combs < 1 ||
         n_combs > 8 || n_allpass < 1 || stereo_spread < 0)
-        return fail(MST_ERR_ARG, "mst_fx_algorithmic_reverb: bad argument");
+        return fail(MST_ERR_ARG, (name + ": bad argument").c_str());
     if (scratch_bytes < mst_fx_algorithmic_reverb_scratch_bytes(n_items, L, n_combs))
-        return fail(MST_ERR_WORKSPACE, "mst_fx_algorithmic_reverb: scratch too small");
+        return fail(MST_ERR_WORKSPACE, (name + ": scratch too small").c_str());
     CombArgs a;
     a.x = x;
     a.y = scratch + (size_t)n_items * 2 * L;            // [n_combs][n_items * 2][L] behind the wet buffer
@@ -1393,28 +1510,53 @@ extern "C" int mst_fx_algorithmic_reverb(const float *x, float *y, int n_items, 
     a.n_combs = n_combs;
     for (int k = 0; k < n_combs; ++k) {
         if (comb_delays[k] < 1 || comb_delays[k] + stereo_spread > 2048)
-            return fail(MST_ERR_UNSUPPORTED, "mst_fx_algorithmic_reverb: comb delays up to 2048 samples");
+            return fail(MST_ERR_UNSUPPORTED, (name + ": comb delays up to 2048 samples").c_str());
         a.delay[k][0] = comb_delays[k];
         a.delay[k][1] = comb_delays[k] + stereo_spread;
     }
     a.damp = damping;
     a.feedback = room_size;
     a.in_gain = in_gain;
-    MST_LAUNCH(fx_comb_kernel, dim3(n_combs, n_items * 2), dim3(64), stream, a);
+    if (params_dev) MST_LAUNCH(fxsi_comb_kernel, dim3(n_combs, n_items * 2), dim3(64), stream, a, params_dev);
+    else MST_LAUNCH(fx_comb_kernel, dim3(n_combs, n_items * 2), dim3(64), stream, a);
     MST_CHECK_LAUNCH("fx_comb_kernel");
     double *wet = scratch;                                // [n_items * 2][L]
     for (int k = 0; k < n_allpass; ++k) {
         const int dl = allpass_delays[2 * k], dr = allpass_delays[2 * k + 1];
-        if (dl < 1 || dr < 1) return fail(MST_ERR_ARG, "mst_fx_algorithmic_reverb: all-pass delay < 1");
+        if (dl < 1 || dr < 1) return fail(MST_ERR_ARG, (name + ": all-pass delay < 1").c_str());
         const int threads = std::min(1024, std::max(64, ((std::max(dl, dr) + 63) / 64) * 64));
-        MST_LAUNCH(fx_allpass_kernel, dim3(n_items * 2), dim3(threads), stream, wet, (const double *)a.y, k == 0 ? n_combs : 0, 0, L,
-                   n_items * 2, dl, dr, room_size);
+        if (params_dev)
+            MST_LAUNCH(fxsi_allpass_kernel, dim3(n_items * 2), dim3(threads), stream, wet, (const double *)a.y, k == 0 ? n_combs : 0, 0, L,
+                       n_items * 2, dl, dr, params_dev);
+        else
+            MST_LAUNCH(fx_allpass_kernel, dim3(n_items * 2), dim3(threads), stream, wet, (const double *)a.y, k == 0 ? n_combs : 0, 0, L,
+                       n_items * 2, dl, dr, room_size);
         MST_CHECK_LAUNCH("fx_allpass_kernel");
     }
-    MST_LAUNCH(fx_reverb_mix_kernel, dim3((unsigned)((L + 255) / 256), n_items), dim3(256), stream, x, (const double *)wet, y, L, C, wet1,
-               wet2, dry);
+    if (params_dev)
+        MST_LAUNCH(fxsi_reverb_mix_kernel, dim3((unsigned)((L + 255) / 256), n_items), dim3(256), stream, x, (const double *)wet, y, L, C, params_dev);
+    else
+        MST_LAUNCH(fx_reverb_mix_kernel, dim3((unsigned)((L + 255) / 256), n_items), dim3(256), stream, x, (const double *)wet, y, L, C, wet1,
+                   wet2, dry);
     MST_CHECK_LAUNCH("fx_reverb_mix_kernel");
     return MST_OK;
+}
+}  // namespace
+
+extern "C" int mst_fx_algorithmic_reverb(const float *x, float *y, int n_items, long L, int C, const int *comb_delays, int n_combs,
+                                         const int *allpass_delays, int n_allpass, int stereo_spread, double damping, double room_size,
+                                         double in_gain, double wet1, double wet2, double dry, double *scratch, size_t scratch_bytes,
+                                         void *stream) {
+    return reverb_run("mst_fx_algorithmic_reverb", x, y, n_items, L, C, comb_delays, n_combs, allpass_delays, n_allpass, stereo_spread, damping,
+                      room_size, in_gain, wet1, wet2, dry, nullptr, scratch, scratch_bytes, stream);
+}
+
+extern "C" int mst_fx_algorithmic_reverb_items(const float *x, float *y, int n_items, long L, int C, const int *comb_delays, int n_combs,
+                                               const int *allpass_delays, int n_allpass, int stereo_spread, double in_gain,
+                                               const double *params_dev, double *scratch, size_t scratch_bytes, void *stream) {
+    if (!params_dev || n_items > 32767) return fail(MST_ERR_ARG, "mst_fx_algorithmic_reverb_items: bad argument");
+    return reverb_run("mst_fx_algorithmic_reverb_items", x, y, n_items, L, C, comb_delays, n_combs, allpass_delays, n_allpass, stereo_spread, 0.0,
+                      0.0, in_gain, 0.0, 0.0, 0.0, params_dev, scratch, scratch_bytes, stream);
 }
 
 // ---- multi-scale spectral distance (csrc/mss_kernels.h) ------------------------------------------------------------------

@@ -578,6 +578,112 @@ class ConvolutionalReverb(Processor):
         return d.out(y)
 
 
+    MAX_TRANSFORM_BLOCKS = 65535      # transform blocks of one call (a grid axis): mst_fx_convolver_create / mst_fx_convolve_items_prepare
+
+    @staticmethod
+    def _blocks_per_sequence(L, Lh_max):
+        """(n_fft, blocks per (item, channel)) of mst_fx_convolver_create(L, Lh_max, ...): one block up to 2^18 points, overlap-save beyond"""
+        n = 4
+        while n < L + Lh_max - 1:
+            n <<= 1
+        if n > (1 << 18):
+            nh = 1 << max(0, (Lh_max - 1).bit_length())
+            nblk = max(4 * nh, 1 << 16)
+            if nblk > (1 << 21):
+                nblk = 2 * nh
+            if nblk < n:
+                step = nblk - (Lh_max - 1)
+                return nblk, (L + Lh_max - 1 + step - 1) // step
+        return n, 1
+
+    def _response_of(self, values):
+        """The response update() builds for these parameter values; the processor's own values and response are left as they were."""
+        keep, h = parameter_values(self), getattr(self, "h", None)
+        try:
+            for k, v in values.items():
+                getattr(self.parameters, k).value = v
+            self.update()
+            return self.h
+        finally:
+            for k, v in keep.items():
+                getattr(self.parameters, k).value = v
+            if h is None:
+                del self.h
+            else:
+                self.h = h
+
+    def process_items(self, x, values, responses=None):
+        """x [n_items, L, C]; values: one {parameter name: value} per item; responses[i]: the [Lh_i, C] response of item i as process() would
+        use it (AugmentationChain's plan adapts it to the channel count; None: update()'s response for values[i], which must then have the
+        audio's channel count or be mono).  One mst_fx_convolve_items call on a convolver sized for the batch and its longest response: the
+        distinct responses (by identity, then by the fingerprint process() keys its device cache with) go back to back into one bank and are
+        transformed once each; the peak position + pre-delay offset is found per distinct response on the host like process() does.  A batch
+        beyond the 65535-block limit of one call is split into the fewest sub-batches."""
+        d = _items_dev(x, values)
+        if responses is None:
+            responses = [self._response_of(v) for v in values]
+            responses = [np.hstack([h] * d.C) if h.shape[1] == 1 and d.C > 1 else h for h in responses]
+        if len(responses) != d.n:
+            raise ValueError("process_items: one response per item")
+        by_id, by_print, distinct, which = {}, {}, [], []
+        for h in responses:
+            r = by_id.get(id(h))
+            if r is None:
+                if h.ndim != 2 or h.shape[1] != d.C:
+                    raise ValueError(f"impulse response has shape {h.shape}, audio has {d.C} channels")
+                flat = h.reshape(-1)
+                probe = flat[::max(1, flat.shape[0] // 64)][:64]
+                key = (h.shape, str(h.dtype), probe.tobytes(), float(flat.sum(dtype=np.float64)))
+                r = by_print.get(key)
+                if r is None:
+                    r = len(distinct)
+                    distinct.append((h, int(np.argmax(np.max(np.abs(h), axis=1), axis=0))))
+                    by_print[key] = r
+                by_id[id(h)] = r
+            which.append(r)
+        lens = [h.shape[0] for h, _ in distinct]
+        starts = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+        params = np.empty((d.n, 4), dtype=np.float64)
+        for i, (v, r) in enumerate(zip(values, which)):
+            idx = distinct[r][1] + int(0.001 * np.abs(_value(self, v, "pre_delay")) * self.sample_rate)
+            params[i] = (r, int(np.clip(idx, 0, lens[r] - 1)), float(_value(self, v, "dry")), float(_value(self, v, "wet")))
+        bank = d.upload(np.concatenate([np.ascontiguousarray(h, dtype=np.float32) for h, _ in distinct], axis=0))
+        lh_max = max(lens)
+        cap = max(lh_max, 1 << max(0, (lh_max - 1).bit_length()))          # the capacity _convolver gives a new convolver
+        while True:
+            self.last_n_fft, nb = self._blocks_per_sequence(d.L, cap)
+            room = self.MAX_TRANSFORM_BLOCKS // d.C - len(distinct)
+            per_call = room // nb if room >= nb else self.MAX_TRANSFORM_BLOCKS // (d.C * (nb + 1))
+            if per_call < 1:
+                raise NotImplementedError("ConvolutionalReverb.process_items: one item needs more than 65535 transform blocks")
+            calls = -(-d.n // per_call)
+            m = -(-d.n // calls)
+            cv = self._convolver(d.lib, d.L, lh_max, m, d.C, d.x.device)
+            kept = self._convolvers[(d.lib.path, d.L, m, d.C, str(d.x.device))][1]
+            if kept == cap:
+                break
+            cap = kept          # an earlier call left a convolver for longer responses: its geometry decides
+        y = torch.empty_like(d.x)
+        lens64 = np.asarray(lens, dtype=np.int64)
+        for lo in range(0, d.n, m):
+            hi = min(d.n, lo + m)
+            nbytes = d.lib.mst_fx_convolve_items_table_bytes(hi - lo, len(distinct))
+            table = torch.empty(nbytes // 8, dtype=torch.float64)
+            if d.x.is_cuda:
+                table = table.pin_memory()
+            bad = C.c_int(-1)
+            sub = np.ascontiguousarray(params[lo:hi])
+            d.lib.check(d.lib.mst_fx_convolve_items_prepare(cv, starts.ctypes.data, lens64.ctypes.data, len(distinct), int(bank.shape[0]),
+                                                            sub.ctypes.data, hi - lo, table.data_ptr(), nbytes, C.byref(bad)),
+                        "mst_fx_convolve_items_prepare")
+            td = table.to(d.x.device, non_blocking=True) if d.x.is_cuda else d.lib.to_device(table)
+            wbytes = d.lib.mst_fx_convolver_items_workspace_bytes(cv, len(distinct))
+            ws = torch.empty(wbytes, dtype=torch.uint8, device=d.x.device)
+            d.lib.check(d.lib.mst_fx_convolve_items(cv, d.x[lo:hi].data_ptr(), bank.data_ptr(), td.data_ptr(), hi - lo, len(distinct),
+                                                    y[lo:hi].data_ptr(), ws.data_ptr(), wbytes, d.stream), "mst_fx_convolve_items")
+        return d.out(y)
+
+
 class Haas(Processor):
     """Haas effect: one channel gets `feedback` times a circularly delayed copy of itself added (reference
     common_audioeffects.py:768-856; np.roll wraps around, the delay may be negative).  Mono input becomes stereo."""
@@ -604,6 +710,22 @@ class Haas(Processor):
                     "mst_fx_haas")
         return d.out(y)
 
+    def process_items(self, x, values):
+        """x [n_items, L, C]; values: one {'delay', 'feedback', 'wet_channel'} per item - one mst_fx_haas_items call; a wet channel that is
+        neither 'left' nor 'right' leaves that item a copy of its (stereo-expanded) input, like process()."""
+        d = _items_dev(x, values)
+        assert d.C == 1 or d.C == 2, "Haas effect only works with monaural or stereo audio."
+        n = d.n
+        buf = np.empty(20 * n, dtype=np.uint8)          # one upload: int64 delays, float64 feedbacks, int32 wet channels
+        buf[:8 * n].view(np.int64)[:] = [int(_value(self, v, "delay")) for v in values]
+        buf[8 * n:16 * n].view(np.float64)[:] = [float(_value(self, v, "feedback")) for v in values]
+        buf[16 * n:].view(np.int32)[:] = [{"left": 0, "right": 1}.get(_value(self, v, "wet_channel"), -1) for v in values]
+        bd = d.upload(buf)
+        y = torch.empty((d.n, d.L, 2), dtype=torch.float32, device=d.x.device)
+        d.lib.check(d.lib.mst_fx_haas_items(d.x.data_ptr(), y.data_ptr(), d.n, d.L, d.C, bd.data_ptr(), bd.data_ptr() + 8 * n,
+                                            bd.data_ptr() + 16 * n, d.stream), "mst_fx_haas_items")
+        return d.out(y)
+
     def update(self, parameter_name=None):
         self.reset_state()
 
@@ -623,17 +745,31 @@ class Panner(Processor):
             self.parameters.add(Parameter("pan_law", "-4.5dB", "string", options=["-4.5dB", "linear", "constant_power"]))
         self.update()
 
-    def _calculate_pan_coefficents(self):
-        """Left/right gains of the chosen law; kept in the processor dtype (float32) like the reference's self.gains."""
-        frac = float(self.parameters.pan.value)                  # 0 = hard left ... 1 = hard right
+    def _pan_gains(self, values=None):
+        """Left/right gains of the chosen law for the current parameter values, or for `values`; in the processor dtype (float32)."""
+        frac = float(_value(self, values, "pan"))                # 0 = hard left ... 1 = hard right
         theta = frac * (np.pi / 2)
         lin = np.array([((np.pi / 2) - theta) * (2 / np.pi), theta * (2 / np.pi)])
         trig = np.array([np.cos(theta), np.sin(theta)])
-        law = self.parameters.pan_law.value
+        law = _value(self, values, "pan_law")
         table = {"linear": lambda: lin, "constant_power": lambda: trig, "-4.5dB": lambda: np.sqrt(lin * trig)}
         if law not in table:
             raise ValueError(f"Invalid pan_law {law}.")
-        self.gains = table[law]().astype(self.dtype)
+        return table[law]().astype(self.dtype)
+
+    def _calculate_pan_coefficents(self):
+        """Kept in the processor dtype (float32) like the reference's self.gains."""
+        self.gains = self._pan_gains()
+
+    def process_items(self, x, values):
+        """x [n_items, L, C]; values: one {'pan', 'pan_law'} per item - one mst_fx_panner_items call, the gains of every item's pan law from
+        the host (_pan_gains, the arithmetic of update())."""
+        d = _items_dev(x, values)
+        assert d.C == 1 or d.C == 2, "Panner only works with monaural or stereo audio."
+        gd = d.upload(np.stack([self._pan_gains(v) for v in values]).astype(np.float32))
+        y = torch.empty((d.n, d.L, 2), dtype=torch.float32, device=d.x.device)
+        d.lib.check(d.lib.mst_fx_panner_items(d.x.data_ptr(), y.data_ptr(), d.n, d.L, d.C, gd.data_ptr(), d.stream), "mst_fx_panner_items")
+        return d.out(y)
 
     def process(self, x):
         d = _Dev(x)
@@ -675,23 +811,49 @@ class AlgorithmicReverb(Processor):
         self.stereospread = 23
         self.scalegain = 0.2
 
+    def _mix_factors(self, values=None):
+        """(wet1, wet2, dry) of the width-dependent cross-mix, in process()'s arithmetic"""
+        wet_mix, width = _value(self, values, "wet_mix"), _value(self, values, "width")
+        return wet_mix * ((width / 2) + 0.5), wet_mix * ((1 - width) / 2), _value(self, values, "dry_mix")
+
+    def _delays(self):
+        combs = (C.c_int * 4)(*self.COMB_DELAYS[4:])                         # combs 1..4 never reach the output (see above)
+        ap = (C.c_int * 8)(*[v + (self.stereospread if k % 2 else 0) for pair in self.ALLPASS_DELAYS for k, v in enumerate(pair)])
+        return combs, ap
+
     def process(self, data):
         d = _Dev(data)
         if d.C > 2:
             raise ValueError("AlgorithmicReverb needs mono or stereo audio")
         p = self.parameters
-        wet1 = p.wet_mix.value * ((p.width.value / 2) + 0.5)
-        wet2 = p.wet_mix.value * ((1 - p.width.value) / 2)
-        combs = (C.c_int * 4)(*self.COMB_DELAYS[4:])                         # combs 1..4 never reach the output (see above)
-        ap = (C.c_int * 8)(*[v + (self.stereospread if k % 2 else 0) for pair in self.ALLPASS_DELAYS for k, v in enumerate(pair)])
+        wet1, wet2, dry = self._mix_factors()
+        combs, ap = self._delays()
         y = torch.empty(d.n, d.L, 2, dtype=torch.float32, device=d.x.device)
         nbytes = d.lib.mst_fx_algorithmic_reverb_scratch_bytes(d.n, d.L, 4)
         sc = d.scratch((nbytes + 7) // 8)
         d.lib.check(d.lib.mst_fx_algorithmic_reverb(d.x.data_ptr(), y.data_ptr(), d.n, d.L, d.C, combs, 4, ap, 4, self.stereospread,
                                                     float(p.damping.value), float(p.room_size.value), float(self.scalegain), float(wet1),
-                                                    float(wet2), float(p.dry_mix.value), sc.data_ptr(), nbytes, d.stream),
+                                                    float(wet2), float(dry), sc.data_ptr(), nbytes, d.stream),
                     "mst_fx_algorithmic_reverb")
         return d.out(y)
+
+    def process_items(self, x, values):
+        """x [n_items, L, C]; values: one dict of the five parameters per item - one mst_fx_algorithmic_reverb_items call reading
+        [n_items][5] = damping, room_size, wet1, wet2, dry (the mix factors from the host, in process()'s arithmetic)"""
+        d = _items_dev(x, values)
+        if d.C > 2:
+            raise ValueError("AlgorithmicReverb needs mono or stereo audio")
+        rows = [(float(_value(self, v, "damping")), float(_value(self, v, "room_size"))) + tuple(float(f) for f in self._mix_factors(v)) for v in values]
+        pd = d.upload(np.asarray(rows, dtype=np.float64))
+        combs, ap = self._delays()
+        y = torch.empty(d.n, d.L, 2, dtype=torch.float32, device=d.x.device)
+        nbytes = d.lib.mst_fx_algorithmic_reverb_scratch_bytes(d.n, d.L, 4)
+        sc = d.scratch((nbytes + 7) // 8)
+        d.lib.check(d.lib.mst_fx_algorithmic_reverb_items(d.x.data_ptr(), y.data_ptr(), d.n, d.L, d.C, combs, 4, ap, 4, self.stereospread,
+                                                          float(self.scalegain), pd.data_ptr(), sc.data_ptr(), nbytes, d.stream),
+                    "mst_fx_algorithmic_reverb_items")
+        return d.out(y)
+
 
 def _sumsq(d, t):
     out = torch.empty(d.n * SUMSQ_SLOTS, dtype=torch.float64, device=t.device)
@@ -939,7 +1101,11 @@ class AugmentationChain:
         xm = x.materialize()
         if per_item:          # outside the fusion (a short signal, a hard-clipping equaliser, a compressor item to run alone): process_items
             y = fx.process_items(xm, values)
-        else:                 # no per-item form (panner, Haas, the reverbs): item by item through process()
+        elif isinstance(fx, ConvolutionalReverb):          # the response of every item as the plan adapted it
+            y = fx.process_items(xm, values, extras)
+        elif hasattr(fx, "process_items"):                 # panner, Haas, the algorithmic reverb: one per-item call, outside the fusion
+            y = fx.process_items(xm, values)
+        else:                 # a processor type without a per-item form: item by item through process()
             ys = []
             for r, (v, e) in enumerate(zip(values, extras)):
                 self._restore(fx, v, e)

@@ -7,7 +7,11 @@ shared-parameter chain, on one MI355X.  64 segments of [131072, 2] through EQ ->
   (c) chain([x])                               one draw for the whole batch: the work of bench.py's fx_chain leg
 HIP events around each call, the three alternating in one process, ROUNDS rounds of CALLS calls after a warm-up; prints one JSON object
 (median, minimum and maximum of the per-round means, in ms per call) and writes it to --out.  With --builder-only the process runs the
-equaliser's per-item call alone, for a kernel trace of its own (the table builder's time)."""
+equaliser's per-item call alone, for a kernel trace of its own (the table builder's time).
+--chain inst: the "vocals" instrument chain instead (create_inst_effects_augmentation_chain, every probability 1): shuffled EQ / compressor,
+shuffled panner / imager, the convolution reverb in a parallel branch, gain - over a synthetic impulse-response directory the tool writes
+itself (decaying stereo noise, RT60 0.3 ... 3 s, two responses per RT60 group); legs (a) and (b) only.  The record names the transform size the
+batch's convolver ended up with."""
 import argparse
 import json
 import os
@@ -28,6 +32,25 @@ def make_chain():
                              randomize_param_value=True)
 
 
+IR_SECONDS = {"300-600": (0.3, 0.5), "600-1200": (0.8, 1.0), "1200-3000": (1.5, 2.5), "3000-6000": (3.0,)}
+
+
+def make_inst_chain(ir_root):
+    """the "vocals" FX manipulator over synthetic impulse responses written below ir_root: noise whose envelope falls 60 dB in the RT60"""
+    from music_mixing_style_transfer_amd.data_loader import save_wav_pcm16
+    from music_mixing_style_transfer_amd.mixing_manipulator.audio_effects_chain import create_inst_effects_augmentation_chain
+    rng = np.random.default_rng(0)
+    for group, seconds in IR_SECONDS.items():
+        for k, sec in enumerate(seconds):
+            d = os.path.join(ir_root, "IR_set1", "RT60_avg", group, f"room{k}")
+            os.makedirs(d, exist_ok=True)
+            n = int(sec * 44100)
+            h = rng.standard_normal((n, 2)) * np.power(10.0, -3.0 * np.arange(n) / n)[:, None] * 0.5
+            save_wav_pcm16(os.path.join(d, "impulse_response.wav"), h.astype(np.float32))
+    probs = {"eq": 1, "comp": 1, "pan": 1, "imager": 1, "reverb": 1, "gain": 1}
+    return create_inst_effects_augmentation_chain("vocals", probs, ir_dir_path=os.path.join(ir_root, "IR_"))
+
+
 def timed(fn):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
@@ -45,10 +68,17 @@ def main():
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--out", default=None)
     ap.add_argument("--builder-only", action="store_true")
+    ap.add_argument("--chain", choices=["config4", "inst"], default="config4")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     x = (0.1 * torch.randn(a.items, a.length, 2, generator=torch.Generator().manual_seed(0))).clamp_(-1, 1).to(dev)
-    chain = make_chain()
+    tmp = None
+    if a.chain == "inst":
+        import tempfile
+        tmp = tempfile.TemporaryDirectory()
+        chain = make_inst_chain(tmp.name)
+    else:
+        chain = make_chain()
     random.seed(0)
     np.random.seed(0)
     if a.builder_only:
@@ -65,6 +95,8 @@ def main():
     legs = {"call_items": lambda: chain.call_items(x),
             "loop_of_single_items": lambda: [chain([x[i]])[0] for i in range(a.items)],
             "shared_parameters": lambda: chain([x])}
+    if a.chain == "inst":
+        del legs["shared_parameters"]
     for fn in legs.values():          # warm-up: per-device tables, streams, allocator
         fn()
         fn()
@@ -73,13 +105,20 @@ def main():
     for _ in range(a.rounds):
         for k, fn in legs.items():
             means[k].append(statistics.mean(timed(fn) for _ in range(a.calls)))
-    res = {"workload": f"{a.items} x [{a.length}, 2]: EQ -> rms -> compressor -> rms -> imager -> rms -> gain, probability 1, randomised parameters",
+    what = ("EQ -> rms -> compressor -> rms -> imager -> rms -> gain" if a.chain == "config4" else
+            "the vocals instrument chain (shuffled EQ / compressor, shuffled panner / imager, parallel convolution reverb over synthetic responses of 0.3 ... 3 s, gain)")
+    res = {"workload": f"{a.items} x [{a.length}, 2]: {what}, probability 1, randomised parameters",
            "rounds": a.rounds, "calls_per_round": a.calls, "unit": "ms per call (HIP events), median / min / max of the per-round means",
            "device": torch.cuda.get_device_name(0)}
     for k, v in means.items():
         res[k] = {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
     res["call_items_over_loop"] = round(res["call_items"]["median"] / res["loop_of_single_items"]["median"], 4)
-    res["call_items_over_shared"] = round(res["call_items"]["median"] / res["shared_parameters"]["median"], 4)
+    if "shared_parameters" in res:
+        res["call_items_over_shared"] = round(res["call_items"]["median"] / res["shared_parameters"]["median"], 4)
+    if a.chain == "inst":
+        from music_mixing_style_transfer_amd.mixing_manipulator import ConvolutionalReverb
+        rv = next(fx for fx in chain._processors() if isinstance(fx, ConvolutionalReverb))
+        res["convolver_transform_size"] = getattr(rv, "last_n_fft", None)          # of the last call_items batch; None: a build that convolves item by item
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
