@@ -50,7 +50,7 @@ typedef enum {
 
 #define MST_MAX_BLOCKS 32
 
-int mst_version(void);          /* 105: panner, Haas and both reverbs per item, mst_fx_panner_items / mst_fx_haas_items / mst_fx_convolve_items (+ its prepare, table and workspace queries) / mst_fx_algorithmic_reverb_items; 104: mst_tcn_set_fusion / mst_tcn_get_fusion; 103: per-item FX parameters, mst_fx_biquad_cascade_items / mst_fx_compressor_items / mst_fx_midside_imager_items / mst_fx_gain_items; 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
+int mst_version(void);          /* 106: mst_mixfeat_spectral; 105: panner, Haas and both reverbs per item, mst_fx_panner_items / mst_fx_haas_items / mst_fx_convolve_items (+ its prepare, table and workspace queries) / mst_fx_algorithmic_reverb_items; 104: mst_tcn_set_fusion / mst_tcn_get_fusion; 103: per-item FX parameters, mst_fx_biquad_cascade_items / mst_fx_compressor_items / mst_fx_midside_imager_items / mst_fx_gain_items; 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
 const char *mst_last_error(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -634,6 +634,17 @@ int mst_mixfeat_sps(MstMixfeat *h, const float *x_dev, int n_items, long L, cons
  * |X_low_k| / (|X_k| + 1e-5) */
 int mst_mixfeat_low_ratio(MstMixfeat *h, const float *x_low_dev, const float *x_dev, int n_items, long L, int C,
                           const float *scale_low_dev, const float *scale_dev, double *out_dev, void *stream);
+/* The per-frame work of the reference's compute_spectral_features (:509-679: librosa.feature.spectral_centroid / _bandwidth / _rolloff /
+ * _flatness / _contrast).  Since mst_version() 106.  x_dev [n_items][L][C], C = 1 or 2 -> out_dev float64 [n_items][C][T][16]; with S_k,
+ * k = 0 .. n_fft / 2, the float32 magnitudes of a frame and P_k = max(1e-10, S_k^2), everything after them in float64:
+ *   0  sum S_k        1  sum k S_k        2  sum S_k (k - c)^2, c = [1] / [0] (formed from the magnitudes, not from sum k^2 S_k)
+ *   3  the first k whose cumulative sum S_0 + .. + S_k reaches 0.85 [0]        4  sum log P_k        5  sum P_k
+ *   6 + 2 j, 7 + 2 j   the sum of the band_k[j] smallest and of the band_k[j] largest S_k with band_lo[j] <= k < band_hi[j]: exact
+ *                      multiset sums, ties counted once (host arrays; n_bands 1 .. 5 - what 16 numbers hold -, bands non-empty and inside
+ *                      0 .. n_fft / 2 + 1, 1 <= band_k[j] <= band_hi[j] - band_lo[j]; slots of bands beyond n_bands are not written)
+ * All in bins: the caller turns them into Hz.  A frame of digital silence gives exactly 0 in every slot but 4 and 5. */
+int mst_mixfeat_spectral(MstMixfeat *h, const float *x_dev, int n_items, long L, int C, const float *scale_dev, const int *band_lo,
+                         const int *band_hi, const int *band_k, int n_bands, double *out_dev, void *stream);
 /* x_dev [n_items][L][C], C = 1 or 2 -> out_dev float64 [n_items][C][T][3], T = 1 + (L - frame_length) / hop: per frame of frame_length
  * samples sum x^2, sum 20 log10(|x| + 1e-30) and max |x| (a zero sample adds -600 dB, as in get_rms_dynamic_crest) */
 int mst_mixfeat_dynamics(const float *x_dev, int n_items, long L, int C, const float *scale_dev, int frame_length, int hop,

@@ -191,6 +191,8 @@ SIGNATURES = {
     "mst_mixfeat_panning": (C.c_int, [_P, _F, C.c_int, C.c_long, _F, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, _P, _P]),
     "mst_mixfeat_sps": (C.c_int, [_P, _F, C.c_int, C.c_long, _F, _F, _F, _P]),
     "mst_mixfeat_low_ratio": (C.c_int, [_P, _F, _F, C.c_int, C.c_long, C.c_int, _F, _F, _P, _P]),
+    "mst_mixfeat_spectral": (C.c_int, [_P, _F, C.c_int, C.c_long, C.c_int, _F, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                             _P, _P]),
     "mst_mixfeat_dynamics": (C.c_int, [_F, C.c_int, C.c_long, C.c_int, _F, C.c_int, C.c_int, _P, _P]),
     "mst_resample_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(_P)]),
     "mst_resample_destroy": (C.c_int, [_P]),

@@ -210,4 +210,269 @@ __global__ __launch_bounds__(256) void mixfeat_dynamics_kernel(const float *x, l
         o[2] = mx;
     }
 }
+// The spectral epilogue (the issue's MIXFEAT_EPI_SPECTRAL, a kernel of its own): the per-frame work of librosa.feature.spectral_centroid / _bandwidth / _rolloff / _flatness / _contrast
+// (reference compute_spectral_features :509-679).  A sibling of mixfeat_frames_kernel - same load phase, same transform, the magnitudes
+// without the 1e-20 term - because its epilogue is of another kind: a centroid needs the frame's total before the second moment, the
+// roll-off a prefix sum over the bins in natural order, the contrast order statistics inside bands.  After the un-mix every thread
+// holds its magnitudes in registers, `buf` is free, and the 2 G spectra (G frames x the two channels of an item) go back into it in
+// natural bin order, m + 1 floats each (an odd stride: slots of one wave sit on different banks).  From there on, per slot:
+//   sums       TPS = 256 / (2 G) threads; thread j adds the bins j, j + TPS, .. in float64 (consecutive lanes read consecutive words),
+//              xor-shuffles inside the wave, chunks in chunk order through LDS: sum S, sum k S, sum log P, sum P (P = max(1e-10, S^2));
+//              then, with c = sum k S / sum S known to every thread, sum S (k - c)^2 the same way - NOT sum k^2 S - c^2 sum S, which
+//              cancels on a narrow-band frame
+//   roll-off   thread j owns the 17 consecutive bins from 17 j on (stride 17: conflict-free): segment sum, inclusive scan over the slot's
+//              threads (__shfl_up steps, the first wave's total through LDS when a slot spans two waves), then a walk over its own bins;
+//              the answer is the smallest k whose cumulative sum reaches 0.85 sum S (a silent frame: 0 >= 0 at k = 0)
+//   contrast   the sum of the k smallest and of the k largest magnitudes of each band [lo, hi).  Non-negative floats order like their
+//              bit patterns, so the k-th smallest value is the largest pattern v with #{x < v} < k and the k-th largest the largest v
+//              with #{x >= v} >= k: both are built bit by bit from the top, 31 counting passes over the band, shared by the two.  A
+//              (slot, band) task belongs to a group of SW = n_fft / 64 lanes of ONE wave and the band sits in the lanes' registers, so
+//              a pass is compares and an integer xor-shuffle sum: no LDS word, no barrier, no atomic.  The sum is then the values strictly beyond the threshold, in thread
+//              order, plus (k - their count) times the threshold: every tie is counted once.  Tasks are dealt from the top band down,
+//              so the long bands of the slots start on different groups.
+// A frame of digital silence gives 0 in slots 0 .. 3 and 6 .. 15.  The kernel works in bins; the host turns bins into Hz.
+//   grid (groups of G frames, 1, items); x [n_items][L][C]: slot 2 g is channel 0, slot 2 g + 1 channel 1 of frame t0 + g (C == 1: the
+//   same channel again, not stored);  out[((b * C + c) * T + t) * 16 + q], q as in include/mst_hip.h
+#define MIXFEAT_SPEC_OUT 16
+#define MIXFEAT_SPEC_BANDS ((MIXFEAT_SPEC_OUT - 6) / 2)          // bands whose two sums fit behind the six frame sums
+struct MixfeatSelBands {          // bins [lo, hi) and the count k of each band, 1 <= k <= hi - lo, from the host; n <= MIXFEAT_SPEC_BANDS
+    int n;
+    int lo[MIXFEAT_SPEC_BANDS], hi[MIXFEAT_SPEC_BANDS], k[MIXFEAT_SPEC_BANDS];
+};
+
+// The sum of the kq smallest and of the kq largest of mq[lo .. hi) by a group of SW lanes of one wave (lane gl of it); NE * SW >= hi - lo.
+// A lane's values sit in NE registers as bit patterns (past the band: all ones, above every candidate); 31 passes build both thresholds
+// from the top bit, each a count of the registers below two candidates and one integer xor-shuffle sum.  Every lane of the wave calls it.
+template <int NE, int SW>
+__device__ __forceinline__ void mixfeat_select(const float *mq, int lo, int hi, int kq, int gl, double &lsum, double &hsum) {
+    unsigned v[NE];
+#pragma unroll
+    for (int i = 0; i < NE; ++i) {
+        const int k = lo + gl + i * SW;
+        v[i] = k < hi ? __builtin_bit_cast(unsigned, mq[k]) : 0xffffffffu;
+    }
+    unsigned vs = 0u, vl = 0u;          // the kq-th smallest / the kq-th largest pattern
+    for (int bit = 30; bit >= 0; --bit) {
+        const unsigned cs = vs | (1u << bit), cg = vl | (1u << bit);
+        int cnt = 0;          // #{x < cs} + 2^16 #{x < cg}: a band has at most 2049 bins
+#pragma unroll
+        for (int i = 0; i < NE; ++i) cnt += (v[i] < cs ? 1 : 0) + (v[i] < cg ? 0x10000 : 0);
+        for (int s = SW / 2; s >= 1; s >>= 1) cnt += __shfl_xor(cnt, s);
+        if ((cnt & 0xffff) < kq) vs = cs;
+        if (hi - lo - (cnt >> 16) >= kq) vl = cg;
+    }
+    double ls = 0.0, hs = 0.0;
+    int ln = 0, hn = 0;
+#pragma unroll
+    for (int i = 0; i < NE; ++i) {
+        const double x = (double)__builtin_bit_cast(float, v[i]);
+        if (v[i] < vs) { ls += x; ++ln; }
+        if (v[i] > vl && v[i] != 0xffffffffu) { hs += x; ++hn; }
+    }
+    for (int s = SW / 2; s >= 1; s >>= 1) {
+        ls += __shfl_xor(ls, s);
+        hs += __shfl_xor(hs, s);
+        ln += __shfl_xor(ln, s);
+        hn += __shfl_xor(hn, s);
+    }
+    lsum = ls + (double)(kq - ln) * (double)__builtin_bit_cast(float, vs);          // ties at the threshold: as many as are missing
+    hsum = hs + (double)(kq - hn) * (double)__builtin_bit_cast(float, vl);
+}
+
+template <int LOGM>
+__global__ __launch_bounds__(256) void mixfeat_spectral_kernel(const float *x, long item_stride, int C, const float *scale, const float *win,
+                                                               const float2 *tw, const float2 *twn, int hop, int T, MixfeatSelBands bands,
+                                                               double *out) {
+    constexpr int m = 1 << LOGM, n = 2 * m, G = MSS_PTS / n, NS = 2 * G, TPS = 256 / NS;
+    constexpr int CW = TPS < 64 ? TPS : 64, CPS = TPS / CW, NCH = 256 / CW;          // lanes of a chunk, chunks per slot, chunks
+    constexpr int SEG = 17, NSV = (m + TPS) / TPS, SW = 64 >> (11 - LOGM), NG = 256 / SW;          // roll-off segment, strided bins; lanes and number of select groups
+    static_assert(TPS * SEG >= m + 1 && NS * (m + 1) <= 2 * MSS_LDS, "the spectra must fit buf, the segments a spectrum");
+    __shared__ float2 buf[MSS_LDS];
+    __shared__ float2 wl[m / 2];
+    __shared__ double part[NCH][5];
+    __shared__ double wtot[4];
+    __shared__ int rpart[NCH];
+    __shared__ int sb[3][MIXFEAT_SPEC_BANDS];
+    const int tid = threadIdx.x, t0 = blockIdx.x * G;
+    const float *pa = x + (long)blockIdx.z * item_stride, *pb = pa + (C == 2 ? 1 : 0);
+    const float sa = scale ? scale[blockIdx.z] : 1.0f;
+    for (int j = tid; j < m / 2; j += 256) wl[j] = tw[j];
+#pragma unroll
+    for (int j = 0; j < MIXFEAT_SPEC_BANDS; ++j)
+        if (tid == j) { sb[0][j] = bands.lo[j]; sb[1][j] = bands.hi[j]; sb[2][j] = bands.k[j]; }
+    float *fb = (float *)buf;
+#pragma unroll 4
+    for (int e = 0; e < G * n / 256; ++e) {
+        const int q = tid + 256 * e, g = q >> (LOGM + 1), r = q & (n - 1), t = t0 + g;
+        float va = 0.0f, vb = 0.0f;
+        if (t < T) {
+            const long i = ((long)t * hop + r) * C;
+            const float w = win[r];
+            va = w * (pa[i] * sa);
+            vb = w * (pb[i] * sa);
+        }
+        const int ce = (2 * g) * m + (r >> 1);
+        fb[2 * mss_pad(ce) + (r & 1)] = va;
+        fb[2 * mss_pad(ce + m) + (r & 1)] = vb;
+    }
+    __syncthreads();
+    mss_fft<LOGM>(buf, wl, tid);
+
+    // the un-mix of mixfeat_frames_kernel, all of a thread's magnitudes kept: [item of the thread][signal][bin k, bin m - k, bin m, bin 0]
+    float mg[MSS_PTS / 4 / 256][2][4];
+#pragma unroll
+    for (int e = 0; e < MSS_PTS / 4 / 256; ++e) {
+        const int idx = tid + 256 * e, g = idx >> (LOGM - 1), kk = idx & (m / 2 - 1);
+        const int k = kk ? kk : m / 2, kc = m - k;
+        const int pk = mss_pos<LOGM>(k), pc = mss_pos<LOGM>(kc);
+        const float2 w = twn[k];
+#pragma unroll
+        for (int sg = 0; sg < 2; ++sg) {
+            const int o = (2 * g + sg) * m;
+            const float2 a = buf[mss_pad(o + pk)], b = buf[mss_pad(o + pc)];
+            const float ex = 0.5f * (a.x + b.x), ey = 0.5f * (a.y - b.y), dx = 0.5f * (a.x - b.x), dy = 0.5f * (a.y + b.y);
+            const float px = fmaf(w.y, dx, w.x * dy), py = fmaf(w.y, dy, -(w.x * dx));          // -i w D
+            mg[e][sg][0] = mixfeat_mag(ex + px, ey + py);
+            mg[e][sg][1] = mixfeat_mag(ex - px, py - ey);
+            mg[e][sg][2] = mg[e][sg][3] = 0.0f;
+            if (kk == 0) {
+                const float2 z0 = buf[mss_pad(o)];
+                mg[e][sg][2] = mixfeat_mag(z0.x - z0.y, 0.0f);
+                mg[e][sg][3] = mixfeat_mag(z0.x + z0.y, 0.0f);
+            }
+        }
+    }
+    __syncthreads();          // every thread holds its magnitudes: buf is free
+#pragma unroll
+    for (int e = 0; e < MSS_PTS / 4 / 256; ++e) {
+        const int idx = tid + 256 * e, g = idx >> (LOGM - 1), kk = idx & (m / 2 - 1);
+        const int k = kk ? kk : m / 2;
+#pragma unroll
+        for (int sg = 0; sg < 2; ++sg) {
+            float *ms = fb + (2 * g + sg) * (m + 1);
+            ms[k] = mg[e][sg][0];
+            if (kk) {
+                ms[m - k] = mg[e][sg][1];
+            } else {
+                ms[m] = mg[e][sg][2];
+                ms[0] = mg[e][sg][3];
+            }
+        }
+    }
+    __syncthreads();
+
+    const int slot = tid / TPS, j = tid & (TPS - 1), cl = tid & (CW - 1), chunk = tid / CW;
+    const float *ms = fb + slot * (m + 1);
+    // a thread's bins come out of LDS once, into registers: NSV strided ones for the sums, SEG consecutive ones for the roll-off (a loop that
+    // waits for every LDS word it compares costs the LDS latency per bin; bins past m are 0 and add nothing)
+    float sv[NSV], cv[SEG];
+#pragma unroll
+    for (int i = 0; i < NSV; ++i) sv[i] = j + i * TPS <= m ? ms[j + i * TPS] : 0.0f;
+    const int k0 = j * SEG;
+#pragma unroll
+    for (int i = 0; i < SEG; ++i) cv[i] = k0 + i <= m ? ms[k0 + i] : 0.0f;
+    {          // sum S, sum k S, sum log P, sum P
+        double a0 = 0.0, a1 = 0.0, a4 = 0.0, a5 = 0.0;
+#pragma unroll
+        for (int i = 0; i < NSV; ++i) {
+            const int k = j + i * TPS;
+            if (k <= m) {
+                const double s = (double)sv[i], p = fmax(1e-10, s * s);
+                a0 += s;
+                a1 += (double)k * s;
+                a4 += log(p);
+                a5 += p;
+            }
+        }
+        for (int s = CW / 2; s >= 1; s >>= 1) {
+            a0 += __shfl_xor(a0, s);
+            a1 += __shfl_xor(a1, s);
+            a4 += __shfl_xor(a4, s);
+            a5 += __shfl_xor(a5, s);
+        }
+        if (cl == 0) { part[chunk][0] = a0; part[chunk][1] = a1; part[chunk][3] = a4; part[chunk][4] = a5; }
+    }
+    // the roll-off's scan does not need the total: segment sums and their inclusive scan over the slot's threads
+    double inc = 0.0;
+#pragma unroll
+    for (int i = 0; i < SEG; ++i) inc += (double)cv[i];
+    for (int d = 1; d < CW; d <<= 1) {
+        const double v = __shfl_up(inc, d);
+        if (cl >= d) inc += v;
+    }
+    double cum = __shfl_up(inc, 1);          // exclusive: what lies below the thread's first bin
+    if (cl == 0) cum = 0.0;
+    if ((tid & 63) == 63) wtot[tid >> 6] = inc;
+    __syncthreads();
+    double s0 = 0.0, s1 = 0.0;
+    for (int c = 0; c < CPS; ++c) {
+        s0 += part[slot * CPS + c][0];
+        s1 += part[slot * CPS + c][1];
+    }
+    if (CPS == 2 && (chunk & 1)) cum += wtot[chunk - 1];
+    {          // sum S (k - c)^2 and the first bin whose cumulative sum reaches 0.85 sum S
+        const double cb = s0 > 0.0 ? s1 / s0 : 0.0, thr = 0.85 * s0;
+        double a2 = 0.0;
+#pragma unroll
+        for (int i = 0; i < NSV; ++i) {
+            const double d = (double)(j + i * TPS) - cb;
+            a2 += (double)sv[i] * (d * d);
+        }
+        int first = m;
+#pragma unroll
+        for (int i = 0; i < SEG; ++i) {
+            cum += (double)cv[i];
+            if (k0 + i <= m && cum >= thr && k0 + i < first) first = k0 + i;
+        }
+        for (int s = CW / 2; s >= 1; s >>= 1) {
+            a2 += __shfl_xor(a2, s);
+            const int o = __shfl_xor(first, s);
+            first = o < first ? o : first;
+        }
+        if (cl == 0) { part[chunk][2] = a2; rpart[chunk] = first; }
+    }
+
+    // contrast: (slot, band) tasks, one per group of SW lanes and round, the top band first.  NG = 2 NS, so a round is two bands over all
+    // slots: the longer of the two decides - for the whole workgroup - how many registers per lane the round's values take
+    const int nb = bands.n, ntask = NS * nb, gl = tid & (SW - 1);
+    for (int q0 = 0; q0 < ntask; q0 += NG) {          // uniform: every lane of a wave takes every shuffle
+        const int q = q0 + tid / SW;
+        const bool live = q < ntask;
+        const int bj = live ? nb - 1 - q / NS : 0, sl = q & (NS - 1);
+        const int lo = live ? sb[0][bj] : 0, hi = live ? sb[1][bj] : 0, kq = live ? sb[2][bj] : 1;
+        const int b1 = nb - 1 - q0 / NS, b2 = b1 > 0 ? b1 - 1 : b1;
+        const int len1 = sb[1][b1] - sb[0][b1], len2 = sb[1][b2] - sb[0][b2], longest = len1 > len2 ? len1 : len2;
+        double lsum, hsum;
+        if (longest <= 4 * SW) mixfeat_select<4, SW>(fb + sl * (m + 1), lo, hi, kq, gl, lsum, hsum);
+        else mixfeat_select<(m + SW) / SW, SW>(fb + sl * (m + 1), lo, hi, kq, gl, lsum, hsum);
+        const int t = t0 + (sl >> 1), c = sl & 1;
+        if (live && gl == 0 && t < T && c < C) {
+            double *o = out + (((long)blockIdx.z * C + c) * T + t) * MIXFEAT_SPEC_OUT + 6 + 2 * bj;
+            o[0] = lsum;
+            o[1] = hsum;
+        }
+    }
+    __syncthreads();
+    if (j == 0) {
+        const int t = t0 + (slot >> 1), c = slot & 1;
+        if (t < T && c < C) {
+            double s2 = 0.0, s4 = 0.0, s5 = 0.0;
+            int first = m;
+            for (int cc = 0; cc < CPS; ++cc) {
+                const int ch = slot * CPS + cc;
+                s2 += part[ch][2];
+                s4 += part[ch][3];
+                s5 += part[ch][4];
+                first = rpart[ch] < first ? rpart[ch] : first;
+            }
+            double *o = out + (((long)blockIdx.z * C + c) * T + t) * MIXFEAT_SPEC_OUT;
+            o[0] = s0;
+            o[1] = s1;
+            o[2] = s2;
+            o[3] = (double)first;
+            o[4] = s4;
+            o[5] = s5;
+        }
+    }
+}
 #pragma clang fp contract(on)          // the compiler's default for the rest of the translation unit

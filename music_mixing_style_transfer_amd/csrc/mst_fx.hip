@@ -1823,6 +1823,46 @@ extern "C" int mst_mixfeat_low_ratio(MstMixfeat *h, const float *x_low, const fl
     return mixfeat_launch<MIXFEAT_EPI_LOW_RATIO>(h, x_low, x, n_items, C, L, C, scale_low, scale, bands, out, nullptr, nullptr, stream);
 }
 
+extern "C" int mst_mixfeat_spectral(MstMixfeat *h, const float *x, int n_items, long L, int C, const float *scale, const int *band_lo,
+                                    const int *band_hi, const int *band_k, int n_bands, double *out, void *stream) {
+    int rc;
+    if ((rc = mixfeat_check(h, x, out, n_items, L, "mst_mixfeat_spectral"))) return rc;
+    if (C != 1 && C != 2) return fail(MST_ERR_UNSUPPORTED, "mst_mixfeat_spectral: C = " + std::to_string(C) + " (1 or 2 channels)");
+    if (!band_lo || !band_hi || !band_k) return fail(MST_ERR_ARG, "mst_mixfeat_spectral: null band arrays");
+    if (n_bands < 1 || n_bands > MIXFEAT_SPEC_BANDS)          // the 16 numbers of a frame hold five bands' pairs behind the six sums
+        return fail(MST_ERR_UNSUPPORTED, "mst_mixfeat_spectral: n_bands = " + std::to_string(n_bands) + " (1 .. 5: a frame's 16 numbers hold no more)");
+    MixfeatSelBands bands;
+    bands.n = n_bands;
+    for (int j = 0; j < MIXFEAT_SPEC_BANDS; ++j) {
+        bands.lo[j] = bands.hi[j] = 0;
+        bands.k[j] = 1;
+    }
+    for (int j = 0; j < n_bands; ++j) {
+        if (band_lo[j] < 0 || band_hi[j] <= band_lo[j] || band_hi[j] > h->n_fft / 2 + 1)
+            return fail(MST_ERR_ARG, "mst_mixfeat_spectral: band " + std::to_string(j) + " = [" + std::to_string(band_lo[j]) + ", " +
+                                         std::to_string(band_hi[j]) + ") is empty or not inside 0 .. n_fft / 2 + 1");
+        if (band_k[j] < 1 || band_k[j] > band_hi[j] - band_lo[j])
+            return fail(MST_ERR_ARG, "mst_mixfeat_spectral: band " + std::to_string(j) + ": k = " + std::to_string(band_k[j]) + " (1 .. " +
+                                         std::to_string(band_hi[j] - band_lo[j]) + ", the band's bins)");
+        bands.lo[j] = band_lo[j];
+        bands.hi[j] = band_hi[j];
+        bands.k[j] = band_k[j];
+    }
+    const int T = (int)mixfeat_frames(h, L), G = MSS_PTS / h->n_fft;
+    const dim3 grid((unsigned)((T + G - 1) / G), 1, (unsigned)n_items);
+#define MIXFEAT_CASE(LM)                                                                                                              \
+    case LM:                                                                                                                          \
+        MST_LAUNCH((mixfeat_spectral_kernel<LM>), grid, dim3(256), stream, x, L * C, C, scale, (const float *)h->win,                 \
+                   (const float2 *)h->tw, (const float2 *)h->twn, h->hop, T, bands, out);                                             \
+        break;
+    switch (h->logm) {
+        MIXFEAT_CASE(8) MIXFEAT_CASE(9) MIXFEAT_CASE(10) MIXFEAT_CASE(11)
+    }
+#undef MIXFEAT_CASE
+    MST_CHECK_LAUNCH("mixfeat_spectral_kernel");
+    return MST_OK;
+}
+
 extern "C" int mst_mixfeat_dynamics(const float *x, int n_items, long L, int C, const float *scale, int frame_length, int hop, double *out,
                                     void *stream) {
     if (!x || !out || n_items < 1 || L < 1) return fail(MST_ERR_ARG, "mst_mixfeat_dynamics: bad argument");

@@ -1,15 +1,16 @@
 """Score a transfer against a target on the MI355X:
 
     python -m music_mixing_style_transfer_amd.inference.evaluate --est A.wav --target B.wav [--segment_length N] [--mode midside|ori] [--json OUT]
-                                                                 [--metrics mss,loudness,panning,dynamic] [--feature_fft 2048] [--feature_hop 1024]
+                                                                 [--metrics mss,loudness,panning,dynamic,spectral] [--feature_fft 2048] [--feature_hop 1024]
 
 The multi-scale spectral distance of modules/loss.py between the two files, cut into whole segments (a remainder shorter than a
 segment is dropped; a file shorter than one segment is one segment).  --est / --target may be two directories: every wav file of --est
 is scored against the file of the same name in --target.  Prints ONE JSON line: the mean over all segments and the per-segment values.
 
 --metrics adds the reference's audio-feature errors (mixing_manipulator/utils_data_normalization.py compute_loudness_features /
-compute_panning_features / compute_dynamic_features) of every file pair, over the whole file, under the key "features"; with the default,
-"mss", the line is what it always was."""
+compute_panning_features / compute_dynamic_features / compute_spectral_features) of every file pair, over the whole file, under the key
+"features"; with the default, "mss", the line is what it always was.  "spectral" needs 800 frames of --feature_fft / --feature_hop (the
+reference's running mean of the flatness): a shorter file is refused."""
 import argparse
 import json
 import os
@@ -20,7 +21,7 @@ import torch
 from ..data_loader.loader_utils import load_wav_segment, read_wav_raw
 from ..modules.loss import MultiScale_Spectral_Loss_MidSide_DDSP
 
-METRICS = ("mss", "loudness", "panning", "dynamic")
+METRICS = ("mss", "loudness", "panning", "dynamic", "spectral")
 
 
 def _load(path):
@@ -41,10 +42,12 @@ def segments(est, tgt, segment_length):
 
 
 def feature_errors(e, t, rate, metrics, n_fft, hop, device):
-    """e, t [2, L] -> {"loudness": {...}, "panning": {...}, "dynamic": {...}} for the metrics asked for: the whole file, not segments"""
+    """e, t [2, L] -> {"loudness": {...}, "panning": {...}, "dynamic": {...}, "spectral": {...}} for the metrics asked for: the whole
+    file, not segments"""
     from ..mixing_manipulator import utils_data_normalization as U
-    args = (e.t().contiguous().to(device), t.t().contiguous().to(device), 0, rate, n_fft, hop)
-    fns = {"loudness": U.compute_loudness_features, "panning": U.compute_panning_features, "dynamic": U.compute_dynamic_features}
+    args = (e.t().contiguous().to(device), t.t().contiguous().to(device), 0, rate, n_fft, hop, 2)
+    fns = {"loudness": U.compute_loudness_features, "panning": U.compute_panning_features, "dynamic": U.compute_dynamic_features,
+           "spectral": U.compute_spectral_features}
     return {m: {k: float(v[0]) for k, v in fns[m](args).items()} for m in METRICS[1:] if m in metrics}
 
 
@@ -100,8 +103,14 @@ def main(argv=None):
     else:
         pairs = [(a.est, a.target)]
     loss = MultiScale_Spectral_Loss_MidSide_DDSP(mode=a.mode)
-    files = [score_pair(e, t, loss, a.segment_length, torch.device(a.device), metrics=metrics, feature_fft=a.feature_fft,
-                        feature_hop=a.feature_hop) for e, t in pairs]
+    TooFewFrames = ()          # the feature module is imported only where a feature metric asks for it
+    if "spectral" in metrics:
+        from ..mixing_manipulator.utils_data_normalization import TooFewFrames
+    try:
+        files = [score_pair(e, t, loss, a.segment_length, torch.device(a.device), metrics=metrics, feature_fft=a.feature_fft,
+                            feature_hop=a.feature_hop) for e, t in pairs]
+    except TooFewFrames as err:
+        ap.error(str(err))
     if "mss" in metrics:
         allv = [v for f in files for v in f["segments"]]
         out = {"metric": "multi_scale_spectral_" + a.mode, "mean": sum(allv) / len(allv), "n_segments": len(allv)}

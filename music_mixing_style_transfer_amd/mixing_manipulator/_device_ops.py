@@ -310,6 +310,24 @@ class MixFeat:
                                                 lib.stream_ptr(x)), "mst_mixfeat_low_ratio")
         return out.cpu().numpy()
 
+    def spectral(self, x, bands, scale=None):
+        """x device [n, L, C], C = 1 or 2; bands [(lo, hi, k)] in bins -> float64 numpy [n, C, T, 16] per frame: sum S, sum k S,
+        sum S (k - c)^2, the roll-off bin, sum log P, sum P, then per band the sum of its k smallest and of its k largest magnitudes
+        (include/mst_hip.h, mst_mixfeat_spectral; slots of bands that were not asked for are 0)"""
+        lib = self.lib
+        lib.require_device(x, "mst_mixfeat_spectral")
+        x = _batch(x)
+        if x.dtype != torch.float32:
+            raise ValueError(f"mst_mixfeat_spectral: float32 expected, got {x.dtype}")
+        n, L, Cn = x.shape
+        lo, hi, kk = ((C.c_int * len(bands))(*[int(b[i]) for b in bands]) for i in range(3))
+        keep, sp = _scale_ptr(scale, n, x.device)
+        with lib.device_ctx(x):
+            out = torch.zeros(n, Cn, self.frames(L), 16, dtype=torch.float64, device=x.device)
+            lib.check(lib.mst_mixfeat_spectral(self._handle(x), x.data_ptr(), n, L, Cn, sp, lo, hi, kk, len(bands), out.data_ptr(),
+                                               lib.stream_ptr(x)), "mst_mixfeat_spectral")
+        return out.cpu().numpy()
+
     def __del__(self):
         try:
             for h in self._handles.values():

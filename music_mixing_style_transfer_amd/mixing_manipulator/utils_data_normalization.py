@@ -1,6 +1,7 @@
 """EQ and compressor matching of the input normaliser (reference mixing_manipulator/utils_data_normalization.py:
 get_eq_matching :65-107, get_mean_peak :284-338, compress :340-355, get_comp_matching :357-429), and the audio-feature errors the
-reference judges a mix by (compute_loudness_features / compute_panning_features / compute_dynamic_features :483-905 with their helpers
+reference judges a mix by (compute_loudness_features / compute_spectral_features / compute_panning_features / compute_dynamic_features
+:483-905 with their helpers
 get_running_stats :41-63, get_SPS :109-139, get_panning_rms :682-703, get_rms_dynamic_crest :777-811, lowpassFiltering :813-820,
 get_low_freq_weighting :823-846).
 
@@ -19,7 +20,10 @@ the MI355X:
     low-passed spectrum over the spectrum - runs in csrc/mixfeat_kernels.h on `out` and `tar` as one batch of two items, with
     pyloudnorm.normalize.peak folded into the kernels' loads; the zero-phase Butterworth low-pass is the float64 biquad cascade run
     forwards and backwards; the short per-frame sequences come back to the host, where the running means over 40 frames, the deletion
-    of zero-rms target frames and the errors (sklearn's mean_absolute_percentage_error / mean_squared_error, restated) are float64 numpy.
+    of zero-rms target frames and the errors (sklearn's mean_absolute_percentage_error / mean_squared_error, restated) are float64 numpy;
+  * the spectral feature errors: 16 numbers per frame and channel from mixfeat_spectral_kernel (sums, the roll-off bin, the sums of the k
+    smallest and largest magnitudes of librosa's contrast bands); librosa.feature's arithmetic (0.9.2, restated: the package is not a
+    dependency) turns them into centroid, bandwidth, roll-off, flatness and contrast on the host.
 """
 import numpy as np
 import scipy.signal
@@ -379,3 +383,113 @@ def compute_loudness_features(args_):
     meter = fx_utils.Meter(sr)
     loudness_tar, loudness_out = meter.integrated_loudness(t), meter.integrated_loudness(o)
     return {"d_lufs": [_mape([loudness_tar], [loudness_out])], "d_peak": [_mape([peak_tar_db], [peak_out_db])]}
+
+
+# ------------------------------------------------------------------------------------------------ spectral feature errors
+SPECTRAL_KEYS = ("centroid_mean", "bandwidth_mean", "contrast_l_mean", "contrast_m_mean", "contrast_h_mean", "rolloff_mean", "flatness_mean")
+_N_FLATNESS = 800
+
+
+class TooFewFrames(ValueError):
+    """fewer frames than the running mean of the flatness spans: the reference's own call fails there (sklearn on an empty array)"""
+
+
+def contrast_bands(sr, n_fft, fmin=250.0, n_bands=4, quantile=0.02):
+    """The bands of librosa.feature.spectral_contrast (0.9.2) as [(lo, hi, k)] in bins: band j takes the bins with octa[j] <= f_k <=
+    octa[j + 1], octa = [0, fmin, 2 fmin, ..]; every band but the first also the bin below; the last every bin above, up to n_fft / 2.
+    k = max(1, rint(quantile * that count)); every band but the last then loses its LAST bin from the values, so [lo, hi) are the bins
+    the order statistics are taken over."""
+    m = n_fft // 2
+    freq = np.linspace(0, float(sr) / 2, 1 + m, endpoint=True)
+    octa = np.zeros(n_bands + 2)
+    octa[1:] = fmin * (2.0 ** np.arange(0, n_bands + 1))
+    if np.any(octa[:-1] >= 0.5 * sr):
+        raise ValueError(f"contrast_bands: the band edges {octa[:-1]} must stay below the Nyquist frequency {0.5 * sr}")
+    bands = []
+    for j, (f_low, f_high) in enumerate(zip(octa[:-1], octa[1:])):
+        idx = np.flatnonzero(np.logical_and(freq >= f_low, freq <= f_high))
+        if not len(idx):
+            raise ValueError(f"contrast_bands: no bin between {f_low} and {f_high} Hz at sr = {sr}, n_fft = {n_fft}")
+        lo, hi = int(idx[0]), int(idx[-1]) + 1
+        if j > 0:
+            lo -= 1
+        if j == n_bands:
+            hi = m + 1
+        k = int(max(np.rint(quantile * (hi - lo)), 1))
+        if j < n_bands:
+            hi -= 1
+        if k > hi - lo:
+            raise ValueError(f"contrast_bands: band {j} keeps {hi - lo} bin(s) at sr = {sr}, n_fft = {n_fft}, fewer than the {k} it averages")
+        bands.append((lo, hi, k))
+    return bands
+
+
+def _power_to_db(x):
+    """librosa.power_to_db(x, ref=1.0, amin=1e-10, top_db=80.0) over the whole array"""
+    db = 10.0 * np.log10(np.maximum(1e-10, x))
+    return np.maximum(db, db.max() - 80.0)
+
+
+def spectral_sequences(sums, bands, sr, n_fft):
+    """The kernel's per-frame numbers of ONE channel, [T, 16] (_device_ops.MixFeat.spectral), -> the five librosa.feature sequences:
+    centroid, bandwidth, rolloff, flatness [T] and contrast [len(bands), T]"""
+    sums = np.asarray(sums, dtype=np.float64)
+    m = n_fft // 2
+    step = float(sr) / 2 / m
+    s0, s1, s2, ro, slog, sp = (sums[:, i] for i in range(6))
+    small = s0 < np.finfo(np.float32).tiny                      # librosa.util.normalize: such a column is divided by 1
+    div = np.where(small, 1.0, s0)
+    centroid = step * s1 / div
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cb = np.where(s0 > 0, s1 / s0, 0.0)
+    second = np.where(small, s2 + s0 * (cb - s1) ** 2, s2)      # about the centroid in use: the parallel-axis term where it is not [1] / [0]
+    bandwidth = step * np.sqrt(second / div)
+    flatness = np.exp(slog / (m + 1)) / (sp / (m + 1))
+    k = np.asarray([b[2] for b in bands], dtype=np.float64)[:, None]
+    valley, peak = sums[:, 6:6 + 2 * len(bands):2].T / k, sums[:, 7:7 + 2 * len(bands):2].T / k
+    return centroid, bandwidth, step * ro, flatness, _power_to_db(peak) - _power_to_db(valley)
+
+
+def _running_mean(x, N=40):
+    """the mean of every window of N consecutive values of x (running_mean_std without the std the reference drops here)"""
+    c = np.concatenate(([0.0], np.cumsum(np.asarray(x, dtype=np.float64))))
+    return (c[N:] - c[:-N]) / float(N)
+
+
+def spectral_errors(seq_out, seq_tar):
+    """The host half of compute_spectral_features: per channel the five sequences of spectral_sequences, of `out` and of `tar`, -> the
+    reference's dictionary.  eps = 1 on centroid, bandwidth and roll-off, running means over 40 frames (flatness: 800), MAPE, the mean
+    over the channels."""
+    per = {k: [] for k in SPECTRAL_KEYS}
+    for so, st in zip(seq_out, seq_tar):
+        T = len(st[0])
+        if T < _N_FLATNESS:
+            raise TooFewFrames(f"compute_spectral_features: {T} frames, the running mean of the flatness needs {_N_FLATNESS}")
+        run = _running_mean
+        for key, i in (("centroid_mean", 0), ("bandwidth_mean", 1), ("rolloff_mean", 2)):
+            per[key].append(_mape(run(st[i] + 1.0), run(so[i] + 1.0)))
+        ct_t, ct_o = (np.asarray([run(row) for row in s[4]]) for s in (st, so))
+        per["contrast_l_mean"].append(_mape(ct_t[0], ct_o[0]))
+        per["contrast_m_mean"].append(_mape(np.mean(ct_t[1:4], axis=0), np.mean(ct_o[1:4], axis=0)))
+        per["contrast_h_mean"].append(_mape(ct_t[-1], ct_o[-1]))
+        per["flatness_mean"].append(_mape(run(st[3], _N_FLATNESS), run(so[3], _N_FLATNESS)))
+    spectral_ = {k: [np.mean(per[k])] for k in SPECTRAL_KEYS}
+    spectral_["mape_mean"] = [np.mean([np.mean(per[k]) for k in SPECTRAL_KEYS])]
+    return spectral_
+
+
+def compute_spectral_features(args_):
+    audio_out_, audio_tar_, idx, sr, fft_size, hop_length, channels = args_[:7]
+    both = _pair(audio_out_, audio_tar_)
+    if not 1 <= channels <= min(both.shape[2], 2):
+        raise ValueError(f"compute_spectral_features: channels = {channels} of signals with {both.shape[2]} (1 or 2, at most the signals' own)")
+    xb = both[:, :, :channels].contiguous()
+    mf = D.MixFeat.get(fft_size, hop_length)
+    T = mf.frames(xb.shape[1])
+    if T < _N_FLATNESS:
+        raise TooFewFrames(f"compute_spectral_features: {T} frames, the running mean of the flatness needs {_N_FLATNESS}")
+    bands = contrast_bands(sr, fft_size)
+    gain = _peak_gain(both)                                     # pyloudnorm.normalize.peak: the peak over ALL channels of the signal
+    sums = mf.spectral(xb, bands, gain)                         # [2, channels, T, 16]
+    seq = [[spectral_sequences(sums[i, c], bands, sr, fft_size) for c in range(channels)] for i in range(2)]
+    return spectral_errors(seq[0], seq[1])
