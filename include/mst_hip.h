@@ -50,7 +50,7 @@ typedef enum {
 
 #define MST_MAX_BLOCKS 32
 
-int mst_version(void);          /* 106: mst_mixfeat_spectral; 105: panner, Haas and both reverbs per item, mst_fx_panner_items / mst_fx_haas_items / mst_fx_convolve_items (+ its prepare, table and workspace queries) / mst_fx_algorithmic_reverb_items; 104: mst_tcn_set_fusion / mst_tcn_get_fusion; 103: per-item FX parameters, mst_fx_biquad_cascade_items / mst_fx_compressor_items / mst_fx_midside_imager_items / mst_fx_gain_items; 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
+int mst_version(void);          /* 107: mst_tcn_context; 106: mst_mixfeat_spectral; 105: panner, Haas and both reverbs per item, mst_fx_panner_items / mst_fx_haas_items / mst_fx_convolve_items (+ its prepare, table and workspace queries) / mst_fx_algorithmic_reverb_items; 104: mst_tcn_set_fusion / mst_tcn_get_fusion; 103: per-item FX parameters, mst_fx_biquad_cascade_items / mst_fx_compressor_items / mst_fx_midside_imager_items / mst_fx_gain_items; 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
 const char *mst_last_error(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -167,6 +167,14 @@ int mst_tcn_get_tuning(const MstTcn *tcn, int *flags, int *last_forward_fused_bl
  * may be null. */
 int mst_tcn_set_fusion(MstTcn *tcn, int flags);
 int mst_tcn_get_fusion(const MstTcn *tcn, int *flags, int *last_forward_fused_tail);
+
+/* Context of the net (since mst_version() 107), host only, any handle (the generic path's included): *left / *right = how many input samples
+ * before / after an output sample the forward reads - the blocks' zero paddings summed, ((k-1)*d)/2 per side and block, or (k-1)*d on the left
+ * alone for a causal net; (rf - 1) / 2 = 114681 each side for the default configuration.  A caller that converts a long sequence by windows
+ * reproduces the whole-sequence forward when window [a, b) runs on samples [max(0, a - left), min(L, b + right)) - clipped at the sequence's
+ * ends, NOT extended with zeros: the blocks pad their ACTIVATIONS with zeros, and a zero waveform does not give zero activations - and keeps the
+ * outputs of [a, b) (inference/segmentation.py plan_windows, StyleTransferEngine.convert_stem_seamless).  Either pointer may be null. */
+int mst_tcn_context(const MstTcn *tcn, long *left, long *right);
 
 /* measurement hook (bench.py's roofline leg): between _begin and _end every mst_tcn_forward records HIP events
  * on its stream around each kernel; _end synchronises, writes the AVERAGE milliseconds per forward of

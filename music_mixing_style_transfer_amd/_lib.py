@@ -121,6 +121,7 @@ SIGNATURES = {
     "mst_tcn_get_tuning": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mst_tcn_set_fusion": (C.c_int, [_P, C.c_int]),
     "mst_tcn_get_fusion": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mst_tcn_context": (C.c_int, [_P, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "mst_tcn_timing_begin": (C.c_int, [_P, C.c_int]),
     "mst_tcn_timing_end": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "mst_calib_mainloop": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), _P]),

@@ -617,6 +617,20 @@ extern "C" int mst_tcn_get_fusion(const MstTcn *t, int *flags, int *last_forward
     return MST_OK;
 }
 
+extern "C" int mst_tcn_context(const MstTcn *t, long *left, long *right) {
+    if (!t) return fail(MST_ERR_ARG, "mst_tcn_context: null handle");
+    long l = 0, r = 0;
+    for (int n = 0; n < t->d.nblocks; ++n) {      // the blocks' zero paddings (mst_tcn_create), summed
+        const long span = (long)(t->d.kernel_size - 1) * t->d.dilations[n];
+        const long pad_l = t->d.causal ? span : span / 2;
+        l += pad_l;
+        r += span - pad_l;
+    }
+    if (left) *left = l;
+    if (right) *right = r;
+    return MST_OK;
+}
+
 extern "C" int mst_tcn_timing_begin(MstTcn *t, int max_forwards) {
     if (!t || max_forwards < 1) return fail(MST_ERR_ARG, "mst_tcn_timing_begin: bad argument");
     for (auto e : t->ev) (void)hipEventDestroy(e);

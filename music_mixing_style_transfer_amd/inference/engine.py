@@ -16,6 +16,9 @@ of GPUs.
   * outputs stay sharded: a rank returns the time range [t_lo, t_hi) it produced (the style_transfer runner
     writes each rank's range straight into the output file).  `gather_stem` collects the ranges on ONE rank for
     callers that want the whole stem as a tensor - never an all-gather to everyone.
+
+`convert_stem_seamless` (transfer_stem(seamless=True)) converts the stem as the ONE sequence it is instead: windows with the
+net's real context on both sides, sharded, batched and streamed like the segments.  Off unless asked for.
 """
 import torch
 
@@ -24,6 +27,7 @@ from ..networks import FXencoder, TCNModel
 from . import segmentation as seg
 
 PASS_SAMPLES = 1 << 23          # samples per network pass (64 segments of 131072 / 16 segments of 2**19)
+SEAMLESS_WINDOW = 1 << 21       # seam-free conversion: output samples per window (three interior windows of 2**21 + 2 * 114681 share a pass; halo overhead 10.9 %)
 
 
 def build_models(cfg_encoder, cfg_converter, device, precision="fp32"):
@@ -232,14 +236,115 @@ class StyleTransferEngine:
             d2h.synchronize()
         return out, (t_lo, t_hi)
 
+    # ---- seam-free conversion: the stem as ONE sequence, computed by windows with real context -------------------------------
+    def _window_passes(self, plan, lo, hi, full):
+        """Windows [lo, hi) of `plan` as network passes [(i0, i1), ...]: runs of interior windows (all `full` = W + H_l + H_r
+        samples long, one step of W apart) share a batch of at most pass_samples // full items; a window clipped at an end of the
+        stem is a pass of its own."""
+        per = max(1, self.pass_samples // max(1, full))
+        passes, i = [], lo
+        while i < hi:
+            j = i + 1
+            if plan[i][3] - plan[i][2] == full:
+                while j < hi and j - i < per and plan[j][3] - plan[j][2] == full:
+                    j += 1
+            passes.append((i, j))
+            i = j
+        return passes
+
     @torch.no_grad()
-    def transfer_stem(self, input_stem, reference_stem, segment_length, segment_length_ref, song_name="song"):
+    def convert_stem_seamless(self, input_stem, embedding, window=None, out=None):
+        """This rank's part of the stem converted as the single sequence it is: TCNModel.forward(x[None], e)[0], zero padding only at
+        the stem's true ends, in bounded memory (no reference counterpart; DESIGN.md "Seam-free conversion").  The outputs are cut
+        into windows of `window` samples (default 2**21); window [a, b) runs the net on samples [max(0, a - H_l), min(L, b + H_r))
+        with (H_l, H_r) = TCNModel.context() - clipped at the ends, never extended with zeros - and keeps the outputs of [a, b)
+        (seg.plan_windows).  The windows are sharded over the ranks as contiguous runs; a rank reads and uploads only the samples its
+        own windows need.  Interior windows, all W + H_l + H_r long, run in batches of pass_samples // (W + H_l + H_r) items, clipped
+        windows as items of their own, so no forward sees more than pass_samples samples; a window longer than a pass is an error.
+        Host stems stream one pass ahead on the copy streams, results travel back on the second one.
+
+        embedding: [D], or a callable window index -> [D].  With a callable every window gets its own FiLM row (the batch runs with
+        one condition row per item), and the HALO of a window is computed with THAT window's condition: each window is the
+        whole-sequence forward under its own condition, cut to its range - there is no condition that varies inside one forward.
+
+        Returns (y [2, t_hi - t_lo], (t_lo, t_hi)) like convert_stem: on the device for a device stem, in (pinned) host memory for
+        a host stem (or `out`)."""
+        device = self._device()
+        L = input_stem.shape[-1]
+        W = SEAMLESS_WINDOW if window is None else int(window)
+        h_l, h_r = self.tcn.context()
+        full = W + h_l + h_r
+        plan = seg.plan_windows(L, W, h_l, h_r)
+        if full > self.pass_samples:
+            raise ValueError(f"convert_stem_seamless: a window of {W} samples with its context of {h_l} + {h_r} samples is "
+                             f"{full} samples, more than one pass of {self.pass_samples} samples: lower `window` or raise pass_samples")
+        host = input_stem.device.type == "cpu" and device.type == "cuda"
+        h2d, d2h = self._copy_streams(device) if host else (None, None)
+        lo, hi = seg.shard_range(len(plan), self.rank, self.world)
+        t_lo, t_hi = min(L, lo * W), min(L, hi * W)
+        if out is None:
+            out = torch.empty(2, t_hi - t_lo, dtype=torch.float32, device=input_stem.device, pin_memory=host)
+        per_window = callable(embedding)
+        passes = self._window_passes(plan, lo, hi, full)
+
+        def fetch(i0, i1):
+            """Samples [lo of window i0, hi of window i1 - 1) on the device: every sample of the pass once, though neighbouring windows share their halos."""
+            s0, s1 = plan[i0][2], plan[i1 - 1][3]
+            if not host:
+                return input_stem[:, s0:s1].to(device), None
+            cur = torch.cuda.current_stream(device)
+            with torch.cuda.stream(h2d):
+                slab = torch.empty(2, s1 - s0, dtype=torch.float32, device=device)
+                for c in range(2):
+                    slab[c].copy_(input_stem[c, s0:s1], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(h2d)
+            slab.record_stream(cur)
+            return slab, ev
+
+        pending = []
+        nxt = fetch(*passes[0]) if passes else None
+        for p, (i0, i1) in enumerate(passes):
+            slab, ev = nxt
+            nxt = fetch(*passes[p + 1]) if p + 1 < len(passes) else None          # keep one pass ahead
+            if ev is not None:
+                torch.cuda.current_stream(device).wait_event(ev)
+            n = plan[i0][3] - plan[i0][2]
+            x = slab.unfold(-1, n, W).transpose(0, 1).contiguous()                  # [i1 - i0, 2, n]: window k starts k * W into the slab
+            cond = torch.stack([embedding(i) for i in range(i0, i1)]) if per_window else embedding.unsqueeze(0)
+            y = self.tcn(x, cond)
+            a, b = plan[i0][0], plan[i1 - 1][1]
+            k0 = a - plan[i0][2]                                                    # where the kept range starts inside a window
+            keep = y[:, :, k0:k0 + (b - a if i1 - i0 == 1 else W)].transpose(0, 1).reshape(2, b - a)
+            if host:
+                done = torch.cuda.Event()
+                done.record(torch.cuda.current_stream(device))
+                with torch.cuda.stream(d2h):
+                    d2h.wait_event(done)
+                    for c in range(2):
+                        out[c, a - t_lo:b - t_lo].copy_(keep[c], non_blocking=True)
+                keep.record_stream(d2h)
+                pending.append(keep)
+            else:
+                out[:, a - t_lo:b - t_lo] = keep
+        if host:
+            d2h.synchronize()
+        return out, (t_lo, t_hi)
+
+    @torch.no_grad()
+    def transfer_stem(self, input_stem, reference_stem, segment_length, segment_length_ref, song_name="song", seamless=False,
+                      window=None):
         """One stem end to end (style_transfer.py:123-169).  input_stem / reference_stem: [2, L] tensors, on the device
         or in host memory (pinned host memory overlaps its transfers with the networks); every rank passes the same
         stems and reads only its shard of them.  world == 1: returns the converted stem [2, L_in]; otherwise this
-        rank's (y [2, t_hi - t_lo], (t_lo, t_hi)) - see `gather_stem` / the runner's sliced file writes."""
+        rank's (y [2, t_hi - t_lo], (t_lo, t_hi)) - see `gather_stem` / the runner's sliced file writes.
+        seamless: convert the input as ONE sequence (`convert_stem_seamless`, windows of `window` samples) instead of segment by
+        segment; the reference embedding is the mean over segments either way."""
         emb_avg = self.stem_embedding(reference_stem, segment_length, segment_length_ref, song_name)
-        y, rng = self.convert_stem(input_stem, emb_avg, segment_length, song_name)
+        if seamless:
+            y, rng = self.convert_stem_seamless(input_stem, emb_avg, window)
+        else:
+            y, rng = self.convert_stem(input_stem, emb_avg, segment_length, song_name)
         return y if self.world == 1 else (y, rng)
 
     def gather_stem(self, y_local, t_range, length, dst=0):

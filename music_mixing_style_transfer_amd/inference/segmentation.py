@@ -92,6 +92,24 @@ def check_stackable(ref_length, segment_length, segment_length_ref, batch_size):
                            f"[{n % batch_size}, 2048] at entry {n // batch_size}")
 
 
+def plan_windows(length, window, halo_left, halo_right):
+    """Seam-free conversion (no reference counterpart; DESIGN.md "Seam-free conversion"): [(a, b, lo, hi), ...].  The output
+    ranges [a, b) = [i * window, min(length, (i + 1) * window)) tile [0, length); window i runs the net on samples [lo, hi) =
+    [max(0, a - halo_left), min(length, b + halo_right)) - CLIPPED at the stem's ends, never extended with zeros - and keeps
+    y[:, a - lo : a - lo + (b - a)].  A function of its arguments alone (never of the world size): a window's input, and so
+    its bits, are the same on any number of ranks."""
+    length, window, halo_left, halo_right = int(length), int(window), int(halo_left), int(halo_right)
+    if window < 1:
+        raise ValueError(f"plan_windows: window must be at least 1 sample, got {window}")
+    if length < 0 or halo_left < 0 or halo_right < 0:
+        raise ValueError(f"plan_windows: negative length or halo ({length}, {halo_left}, {halo_right})")
+    plan = []
+    for a in range(0, length, window):
+        b = min(length, a + window)
+        plan.append((a, b, max(0, a - halo_left), min(length, b + halo_right)))
+    return plan
+
+
 def shard_range(n_items, rank, world_size):
     """Contiguous range [lo, hi) of rank `rank`: floor(r*S/N) .. floor((r+1)*S/N)."""
     return (rank * n_items) // world_size, ((rank + 1) * n_items) // world_size

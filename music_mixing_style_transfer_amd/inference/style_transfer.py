@@ -8,6 +8,8 @@ WORLD_SIZE > 1) every stem's segments are sharded across the N GPUs (`inference/
 one all-gather of segment embeddings, canonical-order mean, so the result does not depend on N) and every rank writes its own time
 range of the output files.  The input FX normaliser (--normalize_input True, the reference's default) is implemented
 (mixing_manipulator/data_normalization.py; its BS.1770 meter and onset detector are restatements: parity unpinned).
+--seamless True (no reference counterpart, off by default) converts every input stem as ONE sequence - windows of --seamless_window samples with
+the MixFXcloner's real context on both sides - instead of segment by segment (engine.convert_stem_seamless).
 Not implemented: Demucs separation - the reference shells out to `demucs`; pass --do_not_separate True with the stems already
 under <song>/separated/{input,reference}/ (the default --do_not_separate False raises NotImplementedError).
 
@@ -153,7 +155,8 @@ class Mixing_Style_Transfer_Inference:
                 print(f"\t{inst}...")
                 seg.check_stackable(reference_stems[i].shape[-1], a.segment_length, a.segment_length_ref, a.batch_size)
                 res = eng.transfer_stem(self._host(input_stems[i]), self._host(reference_stems[i]), a.segment_length,
-                                        a.segment_length_ref, dir_name)
+                                        a.segment_length_ref, dir_name, seamless=getattr(a, "seamless", False),
+                                        window=getattr(a, "seamless_window", None))
                 stem_out, t_range = (res, (0, L)) if dist is None else res
                 inst_outputs.append(stem_out)
             mixture = sum(inst_outputs)
@@ -225,7 +228,12 @@ class Mixing_Style_Transfer_Inference:
                         w = (S - 1 - k // a.batch_size) / (S - 1)          # weight by BATCH index, like the reference (:245)
                         out.append(w * emb_a + (1 - w) * emb_b)
                     return torch.stack(out)
-                stem_out, t_range = eng.convert_segments(self._host(input_stems[i]), seg.segment_count(L, seg_len), seg_len, rows)
+                if getattr(a, "seamless", False):
+                    # --seamless: the same pieces and weights, but piece k is a window of the whole stem - its real neighbours as context on
+                    # both sides, under piece k's condition, instead of zero padding at its edges (engine.convert_stem_seamless)
+                    stem_out, t_range = eng.convert_stem_seamless(self._host(input_stems[i]), lambda k: rows(0, k, k + 1)[0], window=seg_len)
+                else:
+                    stem_out, t_range = eng.convert_segments(self._host(input_stems[i]), seg.segment_count(L, seg_len), seg_len, rows)
                 inst_outputs.append(stem_out)
                 if a.save_each_inst:
                     self._write(dist, writers[f"{inst}_{tag}.wav"], t_range[0], stem_out)
@@ -271,6 +279,12 @@ def build_parser():
     i.add_argument("--convert_input", type=str2bool, default=False,
                    help="accept stems at another sample rate (resampled to --sample_rate on the GPU) and 24-bit PCM; off: they raise, "
                         "like the reference.  Outputs are written at --sample_rate either way")
+    i.add_argument("--seamless", type=str2bool, default=False,
+                   help="convert every input stem as ONE sequence (windows with the MixFXcloner's real context, 114681 samples, on both "
+                        "sides) instead of segment by segment with zero padding at every segment edge; off: segments, like the reference.  "
+                        "In --interpolation mode the pieces and weights stay, each piece converted with its real neighbours as context")
+    i.add_argument("--seamless_window", type=int, default=2 ** 21,
+                   help="--seamless: output samples per window (each runs with its context: about 229362 / window more arithmetic)")
     v = p.add_argument_group("Device args")
     v.add_argument("--workers", type=int, default=1)
     v.add_argument("--inference_device", type=str, default="gpu")

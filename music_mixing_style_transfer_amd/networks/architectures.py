@@ -346,6 +346,19 @@ class TCNModel(_DeviceState, nn.Module):
             rf += (hp.kernel_size - 1) * hp.dilation_growth ** (n % hp.stack_size)
         return rf
 
+    def context(self):
+        """(left, right): how many input samples before / after an output sample the net reads - the halo a window of a longer
+        sequence needs to reproduce the whole-sequence forward (inference/segmentation.py plan_windows; mst_tcn_context is the C
+        form).  The blocks' zero paddings summed: (rf - 1) / 2 on each side with rf = compute_receptive_field() for a
+        non-causal net, (rf - 1, 0) for a causal one (all padding on the left)."""
+        hp = self.hparams
+        left = right = 0
+        for blk in self.blocks:
+            span = (hp.kernel_size - 1) * blk.dilation
+            pad_l = span if hp.causal else span // 2
+            left, right = left + pad_l, right + span - pad_l
+        return left, right
+
     @staticmethod
     def add_model_specific_args(parent_parser):
         """The model's hyper-parameters as command-line flags (reference architectures.py:158-174: same names, types and defaults)."""
