@@ -50,7 +50,7 @@ typedef enum {
 
 #define MST_MAX_BLOCKS 32
 
-int mst_version(void);          /* 107: mst_tcn_context; 106: mst_mixfeat_spectral; 105: panner, Haas and both reverbs per item, mst_fx_panner_items / mst_fx_haas_items / mst_fx_convolve_items (+ its prepare, table and workspace queries) / mst_fx_algorithmic_reverb_items; 104: mst_tcn_set_fusion / mst_tcn_get_fusion; 103: per-item FX parameters, mst_fx_biquad_cascade_items / mst_fx_compressor_items / mst_fx_midside_imager_items / mst_fx_gain_items; 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
+int mst_version(void);          /* 108: mst_batch_gather_pcm / mst_batch_finish; 107: mst_tcn_context; 106: mst_mixfeat_spectral; 105: panner, Haas and both reverbs per item, mst_fx_panner_items / mst_fx_haas_items / mst_fx_convolve_items (+ its prepare, table and workspace queries) / mst_fx_algorithmic_reverb_items; 104: mst_tcn_set_fusion / mst_tcn_get_fusion; 103: per-item FX parameters, mst_fx_biquad_cascade_items / mst_fx_compressor_items / mst_fx_midside_imager_items / mst_fx_gain_items; 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
 const char *mst_last_error(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -686,6 +686,24 @@ int mst_resample_taps(const MstResampler *r, float *taps_host, int n);
  * below 2^30 per call, at most 65535 items; y_dev of a stereo call 8-byte aligned. */
 int mst_resample_forward(MstResampler *r, const float *x_dev, long n_in, long in_start, float *y_dev, long n_out, long out_start,
                          int n_items, int C, void *stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Training batches (csrc/batch_kernels.h; data_loader/data_loader.py: the MUSDB datasets).  Since mst_version() 108.  Two streaming launches
+ * around the per-item FX calls: random segments cut out of a resident bank of PCM, and the finishing pass behind the chains.  The tables
+ * are passed twice: *_dev is what the kernel reads, *_host the same values in host memory (pinned, on their way to the device), which
+ * the call checks before it launches anything - a row out of range is MST_ERR_ARG, mst_last_error() names the first one; no device-side
+ * trap.  At most 65535 rows per call.
+ * ---------------------------------------------------------------------------------------------- */
+/* bank_dev: n_bank_frames interleaved stereo frames of `width` (2 or 4) bytes per sample, many files back to back.  table [n] int64: the
+ * first frame of row r (any frame: no alignment beyond one frame; rows may repeat or overlap), 0 <= table[r] and
+ * table[r] + frames <= n_bank_frames.  out_dev float32 [n][frames][2] (8-byte aligned) = int / 2^(8 width - 1) in float64, rounded once to
+ * float32: loader_utils.load_wav_device's arithmetic. */
+int mst_batch_gather_pcm(const void *bank_dev, long n_bank_frames, int width, const long *table_dev, const long *table_host, int n,
+                         long frames, float *out_dev, void *stream);
+/* x_dev float32 [n][Lp][C], C = 1 or 2; rows / start int64 [m]: out_dev [m][C][len], out[r][c][t] = clamp(x[rows[r]][start[r] + t][c], -1, 1)
+ * with torch.clamp's semantics (NaN stays NaN, -0.0 stays -0.0); 0 <= rows[r] < n, 0 <= start[r], start[r] + len <= Lp.  Not in place. */
+int mst_batch_finish(const float *x_dev, int n, long Lp, int C, const long *rows_dev, const long *rows_host, const long *start_dev,
+                     const long *start_host, int m, long len, float *out_dev, void *stream);
 
 #ifdef __cplusplus
 }

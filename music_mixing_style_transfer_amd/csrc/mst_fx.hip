@@ -1,12 +1,13 @@
 // libmst_hip.so, FX-processor part of the C ABI (mst_fx_*): equaliser, compressor, imager, gain, Haas / panner, FFT convolution, STFT,
 // algorithmic reverb, multi-scale spectral distance, mixing-feature metrics - launches of csrc/fx_kernels.h, csrc/fft_kernels.h, csrc/mss_kernels.h and
-// csrc/mixfeat_kernels.h.  See include/mst_hip.h for the contract.
+// csrc/mixfeat_kernels.h - and the training-batch launches mst_batch_* of csrc/batch_kernels.h.  See include/mst_hip.h for the contract.
 #include "mst_host.h"
 #include "fft_kernels.h"
 #include "fx_kernels.h"
 #include "mss_kernels.h"
 #include "mixfeat_kernels.h"
 #include "resample_kernels.h"
+#include "batch_kernels.h"
 
 // =================================================================================================
 // FX processors
@@ -1996,5 +1997,50 @@ extern "C" int mst_resample_forward(MstResampler *r, const float *x, long n_in, 
         MST_LAUNCH(resample_kernel<1>, grid, dim3(RESAMPLE_TILE), stream, x, n_in, in_start, y, n_out, out_start, (const float *)r->taps, r->up,
                    r->down, r->half, r->T);
     MST_CHECK_LAUNCH("resample_kernel");
+    return MST_OK;
+}
+
+// ---- training batches (csrc/batch_kernels.h) -------------------------------------------------------------------------------------
+namespace {
+unsigned batch_grid_x(long groups) { return (unsigned)std::max(1L, (groups + BATCH_GROUPS_PER_BLOCK - 1) / BATCH_GROUPS_PER_BLOCK); }
+}  // namespace
+
+extern "C" int mst_batch_gather_pcm(const void *bank, long n_bank_frames, int width, const long *table_dev, const long *table_host, int n,
+                                    long frames, float *out, void *stream) {
+    if (!bank || !table_dev || !table_host || !out || n < 1 || frames < 1 || n_bank_frames < 1) return fail(MST_ERR_ARG, "mst_batch_gather_pcm: bad argument");
+    if (width != 2 && width != 4) return fail(MST_ERR_ARG, "mst_batch_gather_pcm: width = " + std::to_string(width) + " (2 or 4 bytes per sample)");
+    if (n > 65535) return fail(MST_ERR_UNSUPPORTED, "mst_batch_gather_pcm: n = " + std::to_string(n) + " (at most 65535 rows per call)");
+    if ((uintptr_t)out & 7) return fail(MST_ERR_ARG, "mst_batch_gather_pcm: out_dev must be 8-byte aligned");
+    if (frames > n_bank_frames) return fail(MST_ERR_ARG, "mst_batch_gather_pcm: " + std::to_string(frames) + " frames per row from a bank of " + std::to_string(n_bank_frames));
+    for (int r = 0; r < n; ++r)
+        if (table_host[r] < 0 || table_host[r] > n_bank_frames - frames)
+            return fail(MST_ERR_ARG, "mst_batch_gather_pcm: row " + std::to_string(r) + ": frames " + std::to_string(table_host[r]) + " ... " +
+                                         std::to_string(table_host[r]) + " + " + std::to_string(frames) + " lie outside the bank of " + std::to_string(n_bank_frames));
+    const dim3 grid(batch_grid_x(frames / 4), (unsigned)n);
+    if (width == 2) MST_LAUNCH(batch_gather_pcm_kernel<2>, grid, dim3(BATCH_THREADS), stream, (const unsigned char *)bank, table_dev, out, frames);
+    else MST_LAUNCH(batch_gather_pcm_kernel<4>, grid, dim3(BATCH_THREADS), stream, (const unsigned char *)bank, table_dev, out, frames);
+    MST_CHECK_LAUNCH("batch_gather_pcm_kernel");
+    return MST_OK;
+}
+
+extern "C" int mst_batch_finish(const float *x, int n, long Lp, int C, const long *rows_dev, const long *rows_host, const long *start_dev,
+                                const long *start_host, int m, long len, float *out, void *stream) {
+    if (!x || !rows_dev || !rows_host || !start_dev || !start_host || !out || n < 1 || m < 1 || Lp < 1 || len < 1)
+        return fail(MST_ERR_ARG, "mst_batch_finish: bad argument");
+    if (C != 1 && C != 2) return fail(MST_ERR_ARG, "mst_batch_finish: C = " + std::to_string(C) + " (1 or 2 channels)");
+    if (m > 65535) return fail(MST_ERR_UNSUPPORTED, "mst_batch_finish: m = " + std::to_string(m) + " (at most 65535 rows per call)");
+    if (x == out) return fail(MST_ERR_ARG, "mst_batch_finish: in-place operation is not supported (the layout changes)");
+    if (len > Lp) return fail(MST_ERR_ARG, "mst_batch_finish: len = " + std::to_string(len) + " of rows of " + std::to_string(Lp) + " samples");
+    for (int r = 0; r < m; ++r) {
+        if (rows_host[r] < 0 || rows_host[r] >= n)
+            return fail(MST_ERR_ARG, "mst_batch_finish: row " + std::to_string(r) + ": source row " + std::to_string(rows_host[r]) + " outside [0, " + std::to_string(n) + ")");
+        if (start_host[r] < 0 || start_host[r] > Lp - len)
+            return fail(MST_ERR_ARG, "mst_batch_finish: row " + std::to_string(r) + ": samples " + std::to_string(start_host[r]) + " ... " +
+                                         std::to_string(start_host[r]) + " + " + std::to_string(len) + " lie outside the " + std::to_string(Lp) + " of a row");
+    }
+    const dim3 grid(batch_grid_x(len / 4), (unsigned)m, (unsigned)C);
+    if (C == 2) MST_LAUNCH(batch_finish_kernel<2>, grid, dim3(BATCH_THREADS), stream, x, rows_dev, start_dev, out, Lp, len);
+    else MST_LAUNCH(batch_finish_kernel<1>, grid, dim3(BATCH_THREADS), stream, x, rows_dev, start_dev, out, Lp, len);
+    MST_CHECK_LAUNCH("batch_finish_kernel");
     return MST_OK;
 }

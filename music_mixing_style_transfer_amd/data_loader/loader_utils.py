@@ -118,6 +118,118 @@ def load_wav_device(audio_path, device, sample_rate=44100, preread=None, convert
     return x.t().contiguous()
 
 
+def get_total_audio_length(audio_paths):
+    """frames of all the files together (reference loader_utils.py get_total_audio_length)"""
+    return sum(load_wav_length(p) for p in audio_paths)
+
+
+def _table(values, device):
+    """int64 values as (host tensor, device tensor): the host copy is what the library checks, pinned and on its way to the device"""
+    import torch
+    from .._lib import lib
+    host = torch.from_numpy(np.ascontiguousarray(values, dtype=np.int64))
+    if torch.device(device).type == "cuda":
+        host = host.pin_memory()
+        return host, host.to(device, non_blocking=True)
+    return host, lib().to_device(host)
+
+
+def gather_pcm(bank, n_bank_frames, width, table, frames):
+    """mst_batch_gather_pcm: bank, a uint8 device tensor of n_bank_frames interleaved stereo frames of `width` bytes per sample; table, the
+    first frame of every row -> float32 [len(table), frames, 2], load_wav_device's arithmetic.  A row outside the bank is a ValueError that
+    names it."""
+    import torch
+    from .._lib import lib as _binding
+    lib = _binding()
+    n = len(table)
+    host, dev = _table(table, bank.device)
+    out = torch.empty((n, int(frames), 2), dtype=torch.float32, device=bank.device)
+    with lib.device_ctx(bank):
+        lib.check(lib.mst_batch_gather_pcm(bank.data_ptr(), int(n_bank_frames), int(width), dev.data_ptr(), host.data_ptr(), n, int(frames),
+                                           out.data_ptr(), lib.stream_ptr(bank)), "mst_batch_gather_pcm")
+    return out
+
+
+def batch_finish(x, rows, start, length):
+    """mst_batch_finish: x float32 [n, Lp, C] on the device -> [len(rows), C, length],
+    out[r] = clamp(x[rows[r], start[r]:start[r] + length].T, -1, 1) with torch.clamp's semantics, in one launch."""
+    import torch
+    from .._lib import lib as _binding
+    lib = _binding()
+    if x.dim() != 3 or x.dtype != torch.float32 or len(rows) != len(start):
+        raise ValueError("batch_finish: x must be float32 [n, Lp, C] with one start per row")
+    x = x.contiguous()
+    m = len(rows)
+    rows_host, rows_dev = _table(rows, x.device)
+    start_host, start_dev = _table(start, x.device)
+    out = torch.empty((m, x.shape[2], int(length)), dtype=torch.float32, device=x.device)
+    with lib.device_ctx(x):
+        lib.check(lib.mst_batch_finish(x.data_ptr(), x.shape[0], x.shape[1], x.shape[2], rows_dev.data_ptr(), rows_host.data_ptr(),
+                                       start_dev.data_ptr(), start_host.data_ptr(), m, int(length), out.data_ptr(), lib.stream_ptr(x)),
+                  "mst_batch_finish")
+    return out
+
+
+class StemBank:
+    """The PCM frames of many stereo wav files, read once and kept back to back in ONE buffer, from which `gather` cuts a batch of segments
+    with one launch (csrc/batch_kernels.h).  The files are 16- or 32-bit stereo at sample_rate, all of one bit depth (the reference's
+    ValueErrors otherwise: its loaders raise the same way when a segment is read).  frame_offset[i] / length[i]: where file i starts in the
+    bank and its frames (host arrays).  The buffer lives on the device; a bank larger than max_resident_bytes stays in pinned host memory
+    instead, and gather copies just the chosen ranges into a per-call device slab and rebases its table - the same kernel, the same bits."""
+
+    def __init__(self, paths, device, sample_rate=44100, max_resident_bytes=None):
+        import torch
+        self.paths, self.device, self.sample_rate = list(paths), torch.device(device), sample_rate
+        self.width = None
+        chunks, lengths = [], []
+        for p in self.paths:
+            rate, width, nch, n, raw = read_wav_raw(p)
+            if rate != sample_rate:
+                raise ValueError(f"ValueError: input audio's sample rate should be {sample_rate}")
+            if width not in (2, 4):
+                raise ValueError("ValueError: input audio's bit depth should be 16 or 32-bit")
+            if nch != 2:
+                raise ValueError(f"StemBank: {p}: stereo files only")
+            if self.width is not None and width != self.width:
+                raise ValueError(f"StemBank: {p}: {8 * width}-bit PCM in a bank of {8 * self.width}-bit files (one bit depth per bank)")
+            self.width = width
+            chunks.append(np.frombuffer(raw, dtype=np.uint8, count=n * 2 * width))
+            lengths.append(n)
+        if not chunks:
+            raise ValueError("StemBank: no files")
+        self.length = np.asarray(lengths, dtype=np.int64)
+        self.frame_offset = np.concatenate([[0], np.cumsum(self.length)[:-1]]).astype(np.int64)
+        self.n_frames = int(self.length.sum())
+        self.frame_bytes = 2 * self.width
+        host = torch.from_numpy(np.concatenate(chunks))
+        self.resident = max_resident_bytes is None or host.numel() <= max_resident_bytes
+        if self.device.type == "cuda":
+            self.data = host.to(self.device) if self.resident else host.pin_memory()
+        else:                                       # a test binding whose device memory is host memory
+            self.data = host
+
+    def gather(self, file_idx, start, frames):
+        """Row r = frames start[r] .. start[r] + frames - 1 of file file_idx[r], float32 [n, frames, 2] on the device: int / 2^15 (2^31) in
+        float64 rounded once to float32, bit for bit load_wav_device's values."""
+        import torch
+        file_idx, start, frames = np.asarray(file_idx, dtype=np.int64), np.asarray(start, dtype=np.int64), int(frames)
+        if file_idx.shape != start.shape or file_idx.ndim != 1 or len(file_idx) < 1 or frames < 1:
+            raise ValueError("StemBank.gather: one start per file index and at least one frame")
+        for r, (i, s) in enumerate(zip(file_idx, start)):
+            if not 0 <= i < len(self.paths):
+                raise ValueError(f"StemBank.gather: row {r}: file index {i} outside [0, {len(self.paths)})")
+            if s < 0 or s + frames > self.length[i]:
+                raise ValueError(f"StemBank.gather: row {r}: frames {s} ... {s + frames} lie outside {self.paths[i]} ({self.length[i]} frames)")
+        table = self.frame_offset[file_idx] + start
+        if self.resident:
+            return gather_pcm(self.data, self.n_frames, self.width, table, frames)
+        fb, nb = self.frame_bytes, frames * self.frame_bytes
+        slab = torch.empty(len(table) * nb, dtype=torch.uint8, device=self.device)
+        for r, t in enumerate(table):
+            slab[r * nb:(r + 1) * nb].copy_(self.data[int(t) * fb:int(t) * fb + nb], non_blocking=True)
+        return gather_pcm(slab, len(table) * frames, self.width, np.arange(len(table), dtype=np.int64) * frames, frames)
+
+
 def pcm16_device(x):
     """float device tensor [..., L, C] in [-1, 1] -> int16 tensor, the arithmetic of pcm16(): round-half-even(x * 32767), clipped."""
     import torch

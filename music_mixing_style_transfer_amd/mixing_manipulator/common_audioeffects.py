@@ -1048,6 +1048,34 @@ class AugmentationChain:
         in its order - both generators, every `fxs` order and every parameter value are left as the loop leaves them."""
         return [self._plan_one(channels)[0] for _ in range(n)]
 
+    def plan_one(self, channels):
+        """The draws of ONE `self([a, b, ...])` on arrays with `channels` channels, as a plan for call_plans: what plan_items takes n times."""
+        return self._plan_one(channels)[0]
+
+    def call_plans(self, x, plans, group=1):
+        """x: a batch [len(plans) * group, L, C] (tensor or numpy); row r runs plans[r // group] - the audio half of call_items for plans taken
+        earlier with plan_one / plan_items.  group = 2 is the reference's `self([a, b])`: one set of draws for two arrays (rows 2i and 2i + 1
+        share plan i; a convolution response is shared by identity and transformed once).  Nothing is drawn here; processors are left as they
+        are found (call_items restores them the same way).  Returns what call_items returns."""
+        d0 = _Dev(x)
+        if not d0.batched:
+            raise ValueError("call_plans: x must be a batch [n_items, L, C]")
+        if group < 1 or d0.n != len(plans) * group:
+            raise ValueError(f"call_plans: {d0.n} rows for {len(plans)} plans in groups of {group}")
+        final = [(fx, parameter_values(fx), getattr(fx, "h", None)) for fx in self._processors()]
+        try:
+            rows = self._execute_items(d0, [plans[r // group] for r in range(d0.n)])
+        finally:
+            for fx, values, h in final:
+                self._restore(fx, values, h)
+        if isinstance(rows, torch.Tensor):
+            out = rows
+        elif len({tuple(r.shape) for r in rows}) == 1:
+            out = torch.stack(rows, 0)
+        else:
+            return [r.cpu().numpy() if d0.numpy else r for r in rows]
+        return out.cpu().numpy() if d0.numpy else out
+
     def _processors(self):
         for fx, _, _ in self.fxs:
             if isinstance(fx, Processor):
