@@ -50,7 +50,7 @@ typedef enum {
 
 #define MST_MAX_BLOCKS 32
 
-int mst_version(void);          /* 108: mst_batch_gather_pcm / mst_batch_finish; 107: mst_tcn_context; 106: mst_mixfeat_spectral; 105: panner, Haas and both reverbs per item, mst_fx_panner_items / mst_fx_haas_items / mst_fx_convolve_items (+ its prepare, table and workspace queries) / mst_fx_algorithmic_reverb_items; 104: mst_tcn_set_fusion / mst_tcn_get_fusion; 103: per-item FX parameters, mst_fx_biquad_cascade_items / mst_fx_compressor_items / mst_fx_midside_imager_items / mst_fx_gain_items; 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
+int mst_version(void);          /* 109: mst_mss_backward / mst_mss_backward_workspace_bytes; 108: mst_batch_gather_pcm / mst_batch_finish; 107: mst_tcn_context; 106: mst_mixfeat_spectral; 105: panner, Haas and both reverbs per item, mst_fx_panner_items / mst_fx_haas_items / mst_fx_convolve_items (+ its prepare, table and workspace queries) / mst_fx_algorithmic_reverb_items; 104: mst_tcn_set_fusion / mst_tcn_get_fusion; 103: per-item FX parameters, mst_fx_biquad_cascade_items / mst_fx_compressor_items / mst_fx_midside_imager_items / mst_fx_gain_items; 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
 const char *mst_last_error(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -613,6 +613,18 @@ int mst_mss_forward(MstMss *h, const float *est_dev, const float *tgt_dev, int B
  * [B, C, n_fft / 2, mst_mss_frames()].  The handle's mode and its other scales play no part: L must exceed n_fft / 2 of THIS scale.
  * (Both entry points take at most 65535 items per call: MST_ERR_UNSUPPORTED beyond.) */
 int mst_mss_spectrogram(MstMss *h, int scale, const float *x_dev, int B, int C, long L, float *mag_dev, void *stream);
+/* The gradient of mst_mss_forward's terms with respect to est (since mst_version() 109): the vector-Jacobian product
+ *   grad_est_dev[b] = sum over scales s, channels c of  dterms_dev[b][s][c][0] d S0 / d est + dterms_dev[b][s][c][1] d S1 / d est,
+ * S0, S1 the two sums of (b, s, c) that mst_mss_forward leaves; sgn(0) = 0 as in torch.  Per scale one fused kernel repeats the forward's
+ * transform, forms the per-bin cotangent and runs the adjoint transform in LDS, leaving windowed gradient frames in the workspace; a second
+ * gathers them per sample through the reflection padding and un-mixes mid / side.  The cotangents are read on the device (no host
+ * synchronisation) and rounded to float32.  No atomics: an item's gradient is the same bits in every run and in every batch; est == tgt,
+ * est == 0 and zero cotangents give exact zeros.  grad_est_dev fp32 [B, 2, L] is written, not accumulated.  Limits of mst_mss_forward, and
+ * hop >= n_fft / 16 for every scale (MST_ERR_UNSUPPORTED otherwise; the forward accepts smaller hops).  The workspace is one
+ * [B, 2, T, n_fft] fp32 frames buffer, the largest over the scales. */
+size_t mst_mss_backward_workspace_bytes(const MstMss *h, int B, long L);
+int mst_mss_backward(MstMss *h, const float *est_dev, const float *tgt_dev, int B, long L, const double *dterms_dev, float *grad_est_dev,
+                     void *workspace, size_t workspace_bytes, void *stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Mixing-feature metrics (csrc/mixfeat_kernels.h): the per-frame work of the reference's panning, dynamics and low-frequency features

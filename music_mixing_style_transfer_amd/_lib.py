@@ -186,6 +186,8 @@ SIGNATURES = {
     "mst_mss_workspace_bytes": (C.c_size_t, [_P, C.c_int, C.c_long]),
     "mst_mss_forward": (C.c_int, [_P, _F, _F, C.c_int, C.c_long, _P, _P, C.c_size_t, _P]),
     "mst_mss_spectrogram": (C.c_int, [_P, C.c_int, _F, C.c_int, C.c_int, C.c_long, _F, _P]),
+    "mst_mss_backward_workspace_bytes": (C.c_size_t, [_P, C.c_int, C.c_long]),
+    "mst_mss_backward": (C.c_int, [_P, _F, _F, C.c_int, C.c_long, _P, _F, _P, C.c_size_t, _P]),
     "mst_mixfeat_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(_P)]),
     "mst_mixfeat_destroy": (C.c_int, [_P]),
     "mst_mixfeat_frames": (C.c_int, [_P, C.c_long]),

@@ -1700,6 +1700,47 @@ extern "C" int mst_mss_forward(MstMss *h, const float *est, const float *tgt, in
     return MST_OK;
 }
 
+// one frames workspace [B, 2, T, n_fft] fp32, reused scale after scale: the largest of them
+extern "C" size_t mst_mss_backward_workspace_bytes(const MstMss *h, int B, long L) {
+    if (!h || B < 1 || L < 1) return 0;
+    size_t most = 0;
+    for (int s = 0; s < h->d.n_scales; ++s)
+        most = std::max(most, (size_t)B * 2 * (size_t)std::max(1, mss_frames(h, s, L)) * (size_t)h->d.n_fft[s] * sizeof(float));
+    return 256 + align_up(most, 256);
+}
+
+extern "C" int mst_mss_backward(MstMss *h, const float *est, const float *tgt, int B, long L, const double *dterms, float *grad, void *ws,
+                                size_t ws_bytes, void *stream) {
+    if (!h || !est || !tgt || !dterms || !grad || B < 1 || L < 1) return fail(MST_ERR_ARG, "mst_mss_backward: bad argument");
+    int rc;
+    for (int s = 0; s < h->d.n_scales; ++s)
+        if (h->d.hop[s] * 16 < h->d.n_fft[s])
+            return fail(MST_ERR_UNSUPPORTED, "mst_mss_backward: hop = " + std::to_string(h->d.hop[s]) + " is below n_fft / 16 at n_fft = " +
+                                                 std::to_string(h->d.n_fft[s]) + " (the frames workspace would exceed 16 waveforms per channel)");
+    if ((rc = mss_check_length(h, 0, h->d.n_scales - 1, B, L, "mst_mss_backward"))) return rc;
+    if (!ws || ws_bytes < mst_mss_backward_workspace_bytes(h, B, L)) return fail(MST_ERR_WORKSPACE, "mst_mss_backward: workspace null or too small");
+    float *frames = (float *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    const int mix_mode = h->d.mode == MST_MSS_MIDSIDE ? 1 : 0;
+    for (int s = 0; s < h->d.n_scales; ++s) {
+        const int T = mss_frames(h, s, L);
+        const dim3 grid((unsigned)mss_groups(h, s, L), 2u, (unsigned)B);
+#define MSS_CASE(LM)                                                                                                                  \
+    case LM:                                                                                                                          \
+        MST_LAUNCH((mss_grad_frames_kernel<LM>), grid, dim3(256), stream, est, tgt, 2 * L, (int)L, mix_mode, (const float *)h->win[s],    \
+                   (const float2 *)h->tw[s], (const float2 *)h->twn[s], h->d.hop[s], T, (float)h->d.eps, dterms, h->d.n_scales, s, frames); \
+        break;
+        switch (h->logm[s]) {
+            MSS_CASE(7) MSS_CASE(8) MSS_CASE(9) MSS_CASE(10) MSS_CASE(11)
+        }
+#undef MSS_CASE
+        MST_CHECK_LAUNCH("mss_grad_frames_kernel");
+        MST_LAUNCH(mss_grad_gather_kernel, dim3((unsigned)((L + 255) / 256), (unsigned)B), dim3(256), stream, (const float *)frames, grad, (int)L,
+                   h->d.n_fft[s], h->d.hop[s], T, mix_mode, s > 0 ? 1 : 0);
+        MST_CHECK_LAUNCH("mss_grad_gather_kernel");
+    }
+    return MST_OK;
+}
+
 extern "C" int mst_mss_spectrogram(MstMss *h, int scale, const float *x, int B, int C, long L, float *mag, void *stream) {
     if (!h || !x || !mag || B < 1 || L < 1 || scale < 0 || scale >= h->d.n_scales) return fail(MST_ERR_ARG, "mst_mss_spectrogram: bad argument");
     if (C != 1 && C != 2) return fail(MST_ERR_UNSUPPORTED, "mst_mss_spectrogram: C = " + std::to_string(C) + " (1 or 2 channels)");
