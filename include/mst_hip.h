@@ -50,7 +50,7 @@ typedef enum {
 
 #define MST_MAX_BLOCKS 32
 
-int mst_version(void);          /* 109: mst_mss_backward / mst_mss_backward_workspace_bytes; 108: mst_batch_gather_pcm / mst_batch_finish; 107: mst_tcn_context; 106: mst_mixfeat_spectral; 105: panner, Haas and both reverbs per item, mst_fx_panner_items / mst_fx_haas_items / mst_fx_convolve_items (+ its prepare, table and workspace queries) / mst_fx_algorithmic_reverb_items; 104: mst_tcn_set_fusion / mst_tcn_get_fusion; 103: per-item FX parameters, mst_fx_biquad_cascade_items / mst_fx_compressor_items / mst_fx_midside_imager_items / mst_fx_gain_items; 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
+int mst_version(void);          /* 110: mst_tcn_set_chunk / mst_tcn_get_chunk; 109: mst_mss_backward / mst_mss_backward_workspace_bytes; 108: mst_batch_gather_pcm / mst_batch_finish; 107: mst_tcn_context; 106: mst_mixfeat_spectral; 105: panner, Haas and both reverbs per item, mst_fx_panner_items / mst_fx_haas_items / mst_fx_convolve_items (+ its prepare, table and workspace queries) / mst_fx_algorithmic_reverb_items; 104: mst_tcn_set_fusion / mst_tcn_get_fusion; 103: per-item FX parameters, mst_fx_biquad_cascade_items / mst_fx_compressor_items / mst_fx_midside_imager_items / mst_fx_gain_items; 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
 const char *mst_last_error(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -167,6 +167,26 @@ int mst_tcn_get_tuning(const MstTcn *tcn, int *flags, int *last_forward_fused_bl
  * may be null. */
 int mst_tcn_set_fusion(MstTcn *tcn, int flags);
 int mst_tcn_get_fusion(const MstTcn *tcn, int *flags, int *last_forward_fused_tail);
+
+/* The order of the work over the batch (since mst_version() 110).  Same kernels, same bits: items are independent through the whole net.
+ * A full bf16 forward of a large batch runs in CHUNKS of `items` batch items, every chunk through all blocks (the launch table of an
+ * `items`-sized batch, fused tail included) before the next one starts, two chains of chunks side by side - the caller's stream and a side
+ * stream the handle owns, forked from the caller's stream and joined back into it before the call returns; no device-wide wait, nothing
+ * left pending behind the caller's stream.  Every chunk of a chain reuses the same two activations of the workspace, so the next block finds
+ * the last one's output in the 256 MiB Infinity Cache instead of HBM (measured at 32 x 131072: -2.5 % on the forward).
+ *   items = 0: automatic - chunk only a batch whose ONE activation, B * L * 256 bytes, exceeds the cache, in chunks of the largest count for
+ *     which both chains' two activations fit it (2 at L = 131072; none above L = 262144: the whole batch then).
+ *   items = n >= 1: n items per chunk whatever the size (n >= B, MST_TCN_CHUNK_WHOLE: the whole batch, one launch per block as before).
+ *   items < 0: MST_ERR_ARG.
+ * Where the second chain's two activations do not fit the workspace beside the first's (n > B / 2) the chunks run one after the other on the
+ * caller's stream.  mst_tcn_workspace_bytes is what it was.  fp32, bf16x3, mst_tcn_forward_blocks and the generic path are never chunked.
+ * A handle from mst_tcn_create starts with MST_TCN_CHUNK_WHOLE: its launch table is the one the tuning flags describe.  The Python modules
+ * set 0 (_lib.TCN_CHUNK_DEFAULT).  mst_tcn_get_chunk returns the setting and how many chunks the handle's LAST forward ran (1: the whole
+ * batch); either pointer may be null.  The timing hook below sums a block's launches over the chunks (divided by the number of chains that
+ * ran side by side). */
+#define MST_TCN_CHUNK_WHOLE 0x7fffffff
+int mst_tcn_set_chunk(MstTcn *tcn, int items);
+int mst_tcn_get_chunk(const MstTcn *tcn, int *items, int *ran_chunks);
 
 /* Context of the net (since mst_version() 107), host only, any handle (the generic path's included): *left / *right = how many input samples
  * before / after an output sample the forward reads - the blocks' zero paddings summed, ((k-1)*d)/2 per side and block, or (k-1)*d on the left

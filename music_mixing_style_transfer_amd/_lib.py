@@ -20,6 +20,8 @@ MST_PREC_BF16X3 = 2
 MST_MAX_BLOCKS = 32
 TCN_TUNING_DEFAULT = 245    # mst_tcn_set_tuning flags a fresh handle starts with (include/mst_hip.h: bit 0 bf16x3 small tiles, bits 1-2 = 2 the bf16 class-major family with bit 4 required, bit 5 block 0 fused into block 1, bit 6 bf16x3 half-tile class-major loop, bit 7 bf16 whole-sequence tiles / class-major four-phase head; bit 3 is refused)
 TCN_FUSION_DEFAULT = 1      # mst_tcn_set_fusion flags TCNModel sets on its handle (a raw mst_tcn_create handle starts with 0): bit 0 the last three blocks of a qualifying bf16 forward as one launch
+TCN_CHUNK_DEFAULT = 0       # mst_tcn_set_chunk items TCNModel sets on its handle (a raw mst_tcn_create handle starts with TCN_CHUNK_WHOLE): 0 = a full bf16 forward whose one activation exceeds the Infinity Cache runs in chunks that fit it, on two streams
+TCN_CHUNK_WHOLE = 0x7fffffff
 PRECISIONS = {"fp32": MST_PREC_F32, "f32": MST_PREC_F32, "bf16": MST_PREC_BF16, "bf16x3": MST_PREC_BF16X3}
 
 STATUS_NAMES = {0: "MST_OK", -1: "MST_ERR_ARG", -2: "MST_ERR_UNSUPPORTED", -3: "MST_ERR_HIP", -4: "MST_ERR_STATE",
@@ -121,6 +123,8 @@ SIGNATURES = {
     "mst_tcn_get_tuning": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mst_tcn_set_fusion": (C.c_int, [_P, C.c_int]),
     "mst_tcn_get_fusion": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mst_tcn_set_chunk": (C.c_int, [_P, C.c_int]),
+    "mst_tcn_get_chunk": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mst_tcn_context": (C.c_int, [_P, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "mst_tcn_timing_begin": (C.c_int, [_P, C.c_int]),
     "mst_tcn_timing_end": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_int)]),

@@ -44,10 +44,26 @@ struct MstTcn {
     int last_fused0 = 0;          // whether the last forward of this handle really ran block 0 inside block 1's launch (mst_tcn_get_tuning)
     int fusion = 0;               // mst_tcn_set_fusion flags: launch-level, beside the tuning flags (a fresh handle's launch table is what the tuning flags say)
     int last_fused_tail = 0;      // whether the last forward of this handle ran its last three blocks as one launch (mst_tcn_get_fusion)
-    std::vector<hipEvent_t> ev;   // timing hook: (nblocks + 2) events per recorded forward
-    std::vector<char> ev_tail;    // per recorded forward: its last three blocks were one launch (their events coincide)
-    int ev_max = 0, ev_used = 0;
+    int chunk = MST_TCN_CHUNK_WHOLE;   // mst_tcn_set_chunk: batch items per chunk of a full bf16 forward, 0 = automatic (tcn_chunk_items); like the fusion flags, a fresh handle's launch table is what the tuning flags say
+    int last_chunks = 1;          // how many chunks the last forward of this handle ran (mst_tcn_get_chunk)
+    hipStream_t side = nullptr;   // the second chunk chain's stream and the events of one fork / join: taken on the first chunked forward
+    hipEvent_t side_fork = nullptr, side_join = nullptr;
+    int side_dev = -1;
+    std::vector<hipEvent_t> ev;   // timing hook: (nblocks + 2) events per chunk of a recorded forward (a pool: ev_next of them are taken)
+    struct TimedForward {
+        size_t first;             // its first event in ev
+        int chunks, chains;       // chunks x (nblocks + 2) events; the chunks ran on `chains` streams at a time
+        bool tail;                // its last three blocks were one launch (their events coincide)
+    };
+    std::vector<TimedForward> ev_fwd;
+    size_t ev_next = 0;
+    int ev_max = 0;
 };
+
+// side streams outlive the handles that use them: a destroyed handle's stream (its last work joined into the caller's stream long ago) goes
+// to the next handle that chunks on the same device
+static std::mutex tcn_side_mu;
+static std::vector<std::pair<int, hipStream_t>> tcn_side_free;
 
 
 extern "C" int mst_tcn_create(const MstTcnDesc *desc, MstTcn **out) {
@@ -113,6 +129,12 @@ extern "C" int mst_tcn_destroy(MstTcn *t) {
         (void)hipFree(c.shift);
     }
     for (auto e : t->ev) (void)hipEventDestroy(e);
+    if (t->side_fork) (void)hipEventDestroy(t->side_fork);
+    if (t->side_join) (void)hipEventDestroy(t->side_join);
+    if (t->side_dev >= 0) {
+        std::lock_guard<std::mutex> lock(tcn_side_mu);
+        tcn_side_free.emplace_back(t->side_dev, t->side);
+    }
     delete t;
     return MST_OK;
 }
@@ -430,20 +452,10 @@ int tcn_run_generic(MstTcn *t, const float *x, float *y, float *act_out, int B, 
     return tcn_launch_generic(t->gconv[t->d.nblocks], cur, y, B, L, 2, nullptr, 1, nullptr, 1, stream);
 }
 
-int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, int precision, int n_run, void *ws,
-            size_t ws_bytes, void *stream) {
-    if (!t || !x || B < 1 || L < 1) return fail(MST_ERR_ARG, "mst_tcn_forward: bad argument");
-    if (precision != MST_PREC_F32 && precision != MST_PREC_BF16 && precision != MST_PREC_BF16X3)
-        return fail(MST_ERR_ARG, "mst_tcn_forward: bad precision");
-    for (auto &b : t->blk)
-        if (!b.loaded) return fail(MST_ERR_STATE, "mst_tcn_forward: block weights not loaded");
-    if (!t->out_loaded) return fail(MST_ERR_STATE, "mst_tcn_forward: output conv not loaded");
-    if (t->film_rows == 0) return fail(MST_ERR_STATE, "mst_tcn_forward: mst_tcn_set_cond has not been called");
-    if (t->film_rows != 1 && t->film_rows != B)
-        return fail(MST_ERR_ARG, "mst_tcn_forward: condition rows must be 1 or equal the batch size");
-    const size_t need = mst_tcn_workspace_bytes(t, B, L, precision);
-    if (!ws || ws_bytes < need) return fail(MST_ERR_WORKSPACE, "mst_tcn_forward: workspace too small");
-    if (t->generic) return tcn_run_generic(t, x, y, act_out, B, L, n_run, ws, stream);
+// The launch table of B items: the whole batch, or one chunk of it (tcn_run) - then x and y are the chunk's, film_row0 its first item's FiLM
+// row where the table has a row per item (0 otherwise), buf0 / buf1 the chunk chain's two activations and ev the chunk's nblocks + 2 events.
+int tcn_run_items(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, int precision, int n_run, unsigned char *buf0,
+                  unsigned char *buf1, size_t film_row0, hipEvent_t *ev, void *stream) {
     const int nblocks = t->d.nblocks;
     TcnBlockPlan plan[MST_MAX_BLOCKS] = {};
     for (int n = 1; n < n_run; ++n) {
@@ -467,16 +479,10 @@ int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, i
         }
     }
     t->last_fused_tail = tail ? 1 : 0;
-    const size_t buf_bytes = align_up((size_t)B * L * 128 * tcn_elem(precision), 256);
-    unsigned char *buf[2] = {(unsigned char *)ws, (unsigned char *)ws + buf_bytes};
+    unsigned char *buf[2] = {buf0, buf1};
     const int Lp = L;
-    hipEvent_t *ev = nullptr;
-    if (!act_out && t->ev_used < t->ev_max) {
-        ev = t->ev.data() + (size_t)t->ev_used * (nblocks + 2);
-        t->ev_tail[t->ev_used] = tail ? 1 : 0;
-        t->ev_used++;
-        MST_HIP_TRY(hipEventRecord(ev[0], (hipStream_t)stream));
-    }
+    const float *film = t->film + film_row0 * 256;      // block n's rows: film + n * film_rows * 256
+    if (ev) MST_HIP_TRY(hipEventRecord(ev[0], (hipStream_t)stream));
 
     const bool fuse0 = plan[1].block0;
     t->last_fused0 = fuse0 ? 1 : 0;
@@ -486,7 +492,7 @@ int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, i
         a.y = buf[0];
         a.w = t->blk[0].w_f32;
         a.shift = t->blk[0].shift;
-        a.film = t->film;
+        a.film = film;
         a.res = t->blk[0].res;
         a.film_rows = t->film_rows;
         a.B = B;
@@ -508,7 +514,7 @@ int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, i
         a.y = buf[cur ^ 1];
         a.wpk = precision == MST_PREC_BF16 ? t->blk[n].w_bf16 : (precision == MST_PREC_BF16X3 ? t->blk[n].w_x3 : (void *)t->blk[n].w_f32);
         a.shift = t->blk[n].shift;
-        a.film = t->film + (size_t)n * t->film_rows * 256;
+        a.film = film + (size_t)n * t->film_rows * 256;
         a.res = t->blk[n].res;
         a.film_rows = t->film_rows;
         a.B = B;
@@ -527,7 +533,7 @@ int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, i
             a.x0 = x;
             a.w0pk = t->blk[0].w_bf16;
             a.shift0 = t->blk[0].shift;
-            a.film0 = t->film;
+            a.film0 = film;
             a.res0 = t->blk[0].res;
         }
         if (tail && n == nblocks - 3) {
@@ -539,7 +545,7 @@ int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, i
             for (int k = 0; k < 3; ++k) {
                 ta.wpk[k] = t->blk[n + k].w_bf16;
                 ta.shift[k] = t->blk[n + k].shift;
-                ta.film[k] = t->film + (size_t)(n + k) * t->film_rows * 256;
+                ta.film[k] = film + (size_t)(n + k) * t->film_rows * 256;
                 ta.res[k] = t->blk[n + k].res;
             }
             MST_LAUNCH(tcn_tail_bf16_kernel, dim3((unsigned)p.grid), dim3(256), stream, ta);
@@ -584,6 +590,110 @@ int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, i
     return MST_OK;
 }
 
+// ---- the batch in chunks that stay in the Infinity Cache (mst_tcn_set_chunk; EXPERIMENTS.md E.9) ----
+// Items are independent through the whole net.  As one launch per block over a large batch, a line block k writes is followed by gigabytes of
+// other traffic before block k + 1 reads it: every activation goes to HBM and comes back.  As chunks of c items through ALL blocks, every
+// chunk on the same two ping-pong buffers, block k + 1 finds block k's output on die.  One chain of chunks loses more at its launch seams
+// (c rounds of the chip's workgroup slots per launch instead of B) than the traffic saves; TWO chains on two streams fill each other's
+// seams.  Measured at 32 x 131072 against the full batch, six pairs each: one chain c = 1 / 2 / 4 / 8 / 16 +15.6 / +5.5 / +0.3 / +0.9 /
+// +0.5 % slower; two chains c = 1 / 2 / 3 / 4: -1.3 / -2.5 / -0.3 / 0.0 %.
+constexpr size_t TCN_CACHE_BYTES = (size_t)256 << 20;      // MI355X Infinity Cache
+constexpr int TCN_CHUNK_CHAINS = 2;
+
+// The automatic rule, in bytes, not shapes: a batch whose ONE activation no longer fits the cache (no line can survive from block k to
+// block k + 1) runs in chunks of the largest c whose resident set - two chains x (input + output) x c items - fits it: c = 2 at L = 131072,
+// exactly 256 MiB, the winner of the gate.  c < 1 (an item pair per chain alone overflows the cache: measured break-even) or a batch that
+// fits: the whole batch, as before.
+int tcn_chunk_items(int B, int L) {
+    const size_t item = (size_t)L * 128 * 2;
+    if ((size_t)B * item <= TCN_CACHE_BYTES) return B;
+    const size_t c = TCN_CACHE_BYTES / (2 * TCN_CHUNK_CHAINS * item);
+    return c >= 1 ? (int)c : B;
+}
+
+// the handle's side stream (from the pool of retired ones, or new) and its two events
+int tcn_side_stream(MstTcn *t) {
+    const int dev = mst_current_device();
+    if (t->side_dev >= 0 && t->side_dev != dev) return fail(MST_ERR_STATE, "mst_tcn_forward: the handle's side stream lives on another device");
+    if (t->side_dev >= 0) return MST_OK;
+    if (!t->side_fork) MST_HIP_TRY(hipEventCreateWithFlags(&t->side_fork, hipEventDisableTiming));
+    if (!t->side_join) MST_HIP_TRY(hipEventCreateWithFlags(&t->side_join, hipEventDisableTiming));
+    {
+        std::lock_guard<std::mutex> lock(tcn_side_mu);
+        for (size_t i = 0; i < tcn_side_free.size(); ++i)
+            if (tcn_side_free[i].first == dev) {
+                t->side = tcn_side_free[i].second;
+                t->side_dev = dev;
+                tcn_side_free.erase(tcn_side_free.begin() + i);
+                return MST_OK;
+            }
+    }
+    MST_HIP_TRY(hipStreamCreateWithPriority(&t->side, hipStreamNonBlocking, 0));
+    t->side_dev = dev;
+    return MST_OK;
+}
+
+int tcn_run(MstTcn *t, const float *x, float *y, float *act_out, int B, int L, int precision, int n_run, void *ws,
+            size_t ws_bytes, void *stream) {
+    if (!t || !x || B < 1 || L < 1) return fail(MST_ERR_ARG, "mst_tcn_forward: bad argument");
+    if (precision != MST_PREC_F32 && precision != MST_PREC_BF16 && precision != MST_PREC_BF16X3)
+        return fail(MST_ERR_ARG, "mst_tcn_forward: bad precision");
+    for (auto &b : t->blk)
+        if (!b.loaded) return fail(MST_ERR_STATE, "mst_tcn_forward: block weights not loaded");
+    if (!t->out_loaded) return fail(MST_ERR_STATE, "mst_tcn_forward: output conv not loaded");
+    if (t->film_rows == 0) return fail(MST_ERR_STATE, "mst_tcn_forward: mst_tcn_set_cond has not been called");
+    if (t->film_rows != 1 && t->film_rows != B)
+        return fail(MST_ERR_ARG, "mst_tcn_forward: condition rows must be 1 or equal the batch size");
+    const size_t need = mst_tcn_workspace_bytes(t, B, L, precision);
+    if (!ws || ws_bytes < need) return fail(MST_ERR_WORKSPACE, "mst_tcn_forward: workspace too small");
+    t->last_chunks = 1;
+    if (t->generic) return tcn_run_generic(t, x, y, act_out, B, L, n_run, ws, stream);
+    const int nblocks = t->d.nblocks;
+    const int per = nblocks + 2;
+    // only a full bf16 forward is chunked; the other precisions and the probes keep the whole batch
+    int c = B;
+    if (precision == MST_PREC_BF16 && !act_out && n_run == nblocks && nblocks >= 2) c = std::min(B, t->chunk > 0 ? t->chunk : tcn_chunk_items(B, L));
+    const int chunks = (B + c - 1) / c;
+    const size_t buf_bytes = align_up((size_t)c * L * 128 * tcn_elem(precision), 256);
+    // the second chain needs two buffers of its own inside the same workspace: where they do not fit, one chain on the caller's stream
+    const int chains = chunks >= 2 && 2 * TCN_CHUNK_CHAINS * buf_bytes <= need ? TCN_CHUNK_CHAINS : 1;
+    int rc;
+    if (chains > 1 && (rc = tcn_side_stream(t))) return rc;
+    hipEvent_t *ev = nullptr;
+    if (!act_out && (int)t->ev_fwd.size() < t->ev_max) {
+        while (t->ev.size() < t->ev_next + (size_t)chunks * per) {
+            hipEvent_t e = nullptr;
+            MST_HIP_TRY(hipEventCreate(&e));
+            t->ev.push_back(e);
+        }
+        ev = t->ev.data() + t->ev_next;
+        t->ev_fwd.push_back({t->ev_next, chunks, chains, false});
+        t->ev_next += (size_t)chunks * per;
+    }
+    if (chains > 1) {
+        MST_HIP_TRY(hipEventRecord(t->side_fork, (hipStream_t)stream));
+        MST_HIP_TRY(hipStreamWaitEvent(t->side, t->side_fork, 0));
+    }
+    rc = MST_OK;
+    for (int k = 0; k < chunks && rc == MST_OK; ++k) {
+        const int b0 = k * c, nb = std::min(c, B - b0);
+        const int chain = k % chains;
+        unsigned char *base = (unsigned char *)ws + (size_t)chain * 2 * buf_bytes;
+        rc = tcn_run_items(t, x + (size_t)b0 * t->d.ninputs * L, y ? y + (size_t)b0 * t->d.noutputs * L : nullptr, act_out, nb, L, precision, n_run,
+                           base, base + buf_bytes, t->film_rows > 1 ? (size_t)b0 : 0, ev ? ev + (size_t)k * per : nullptr,
+                           chain ? (void *)t->side : stream);
+    }
+    if (chains > 1) {
+        // joined even after a failed launch: nothing stays pending on the side stream behind the caller's back
+        hipError_t e = hipEventRecord(t->side_join, t->side);
+        if (e == hipSuccess) e = hipStreamWaitEvent((hipStream_t)stream, t->side_join, 0);
+        if (e != hipSuccess && rc == MST_OK) rc = fail(MST_ERR_HIP, std::string("mst_tcn_forward: joining the side stream: ") + hipGetErrorString(e));
+    }
+    if (ev) t->ev_fwd.back().tail = t->last_fused_tail != 0;
+    t->last_chunks = chunks;
+    return rc;
+}
+
 }  // namespace
 
 extern "C" int mst_tcn_set_tuning(MstTcn *t, int flags) {
@@ -617,6 +727,20 @@ extern "C" int mst_tcn_get_fusion(const MstTcn *t, int *flags, int *last_forward
     return MST_OK;
 }
 
+extern "C" int mst_tcn_set_chunk(MstTcn *t, int items) {
+    if (!t) return fail(MST_ERR_ARG, "mst_tcn_set_chunk: null handle");
+    if (items < 0) return fail(MST_ERR_ARG, "mst_tcn_set_chunk: items < 0 (0: automatic, n: n items per chunk, MST_TCN_CHUNK_WHOLE: never)");
+    t->chunk = items;
+    return MST_OK;
+}
+
+extern "C" int mst_tcn_get_chunk(const MstTcn *t, int *items, int *ran_chunks) {
+    if (!t) return fail(MST_ERR_ARG, "mst_tcn_get_chunk: null handle");
+    if (items) *items = t->chunk;
+    if (ran_chunks) *ran_chunks = t->last_chunks;
+    return MST_OK;
+}
+
 extern "C" int mst_tcn_context(const MstTcn *t, long *left, long *right) {
     if (!t) return fail(MST_ERR_ARG, "mst_tcn_context: null handle");
     long l = 0, r = 0;
@@ -634,11 +758,12 @@ extern "C" int mst_tcn_context(const MstTcn *t, long *left, long *right) {
 extern "C" int mst_tcn_timing_begin(MstTcn *t, int max_forwards) {
     if (!t || max_forwards < 1) return fail(MST_ERR_ARG, "mst_tcn_timing_begin: bad argument");
     for (auto e : t->ev) (void)hipEventDestroy(e);
-    t->ev.assign((size_t)max_forwards * (t->d.nblocks + 2), nullptr);
+    t->ev.assign((size_t)max_forwards * (t->d.nblocks + 2), nullptr);      // (a chunked forward takes more: tcn_run creates them as it goes)
     for (auto &e : t->ev) MST_HIP_TRY(hipEventCreate(&e));
-    t->ev_tail.assign((size_t)max_forwards, 0);
+    t->ev_fwd.clear();
+    t->ev_fwd.reserve((size_t)max_forwards);
     t->ev_max = max_forwards;
-    t->ev_used = 0;
+    t->ev_next = 0;
     return MST_OK;
 }
 
@@ -646,22 +771,29 @@ extern "C" int mst_tcn_timing_end(MstTcn *t, float *ms_out, int *n_forwards) {
     if (!t || !ms_out || !n_forwards) return fail(MST_ERR_ARG, "mst_tcn_timing_end: bad argument");
     const int per = t->d.nblocks + 2;
     for (int k = 0; k <= t->d.nblocks; ++k) ms_out[k] = 0.0f;
-    for (int f = 0; f < t->ev_used; ++f) {
-        MST_HIP_TRY(hipEventSynchronize(t->ev[(size_t)f * per + per - 1]));
-        float ms[MST_MAX_BLOCKS + 1] = {};
-        for (int k = 0; k <= t->d.nblocks; ++k) MST_HIP_TRY(hipEventElapsedTime(&ms[k], t->ev[(size_t)f * per + k], t->ev[(size_t)f * per + k + 1]));
-        if (t->ev_tail[f]) {      // the last three blocks were one launch: its time in equal shares
-            const int n0 = t->d.nblocks - 3;
-            ms[n0] = ms[n0 + 1] = ms[n0 + 2] = (ms[n0] + ms[n0 + 1] + ms[n0 + 2]) / 3.0f;
+    const int used = (int)t->ev_fwd.size();
+    for (const MstTcn::TimedForward &f : t->ev_fwd)
+        for (int c = 0; c < f.chunks; ++c) {
+            // a chunked forward: a block's launches summed over the chunks; launches of two chains overlap, each counted in full on its own
+            // stream, so the sum is divided by the number of chains - the figures still add up to about the forward's time
+            const hipEvent_t *ev = t->ev.data() + f.first + (size_t)c * per;
+            MST_HIP_TRY(hipEventSynchronize(ev[per - 1]));
+            float ms[MST_MAX_BLOCKS + 1] = {};
+            for (int k = 0; k <= t->d.nblocks; ++k) MST_HIP_TRY(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+            if (f.tail) {      // the last three blocks were one launch: its time in equal shares
+                const int n0 = t->d.nblocks - 3;
+                ms[n0] = ms[n0 + 1] = ms[n0 + 2] = (ms[n0] + ms[n0 + 1] + ms[n0 + 2]) / 3.0f;
+            }
+            for (int k = 0; k <= t->d.nblocks; ++k) ms_out[k] += ms[k] / (float)f.chains;
         }
-        for (int k = 0; k <= t->d.nblocks; ++k) ms_out[k] += ms[k];
-    }
-    if (t->ev_used > 0)
-        for (int k = 0; k <= t->d.nblocks; ++k) ms_out[k] /= (float)t->ev_used;
-    *n_forwards = t->ev_used;
+    if (used > 0)
+        for (int k = 0; k <= t->d.nblocks; ++k) ms_out[k] /= (float)used;
+    *n_forwards = used;
     for (auto e : t->ev) (void)hipEventDestroy(e);
     t->ev.clear();
-    t->ev_max = t->ev_used = 0;
+    t->ev_fwd.clear();
+    t->ev_max = 0;
+    t->ev_next = 0;
     return MST_OK;
 }
 

@@ -392,6 +392,7 @@ class TCNModel(_DeviceState, nn.Module):
         b.check(b.mst_tcn_create(C.byref(d), C.byref(h)), "mst_tcn_create")
         self._handle, self._lib = h, b
         b.check(b.mst_tcn_set_fusion(h, _lib.TCN_FUSION_DEFAULT), "mst_tcn_set_fusion")
+        b.check(b.mst_tcn_set_chunk(h, _lib.TCN_CHUNK_DEFAULT), "mst_tcn_set_chunk")
         f = lambda t: t.detach().to("cpu", torch.float32).contiguous()
         for n, blk in enumerate(held):
             _load_tcn_block(b, h, n, blk)
