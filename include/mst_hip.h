@@ -50,7 +50,7 @@ typedef enum {
 
 #define MST_MAX_BLOCKS 32
 
-int mst_version(void);          /* 110: mst_tcn_set_chunk / mst_tcn_get_chunk; 109: mst_mss_backward / mst_mss_backward_workspace_bytes; 108: mst_batch_gather_pcm / mst_batch_finish; 107: mst_tcn_context; 106: mst_mixfeat_spectral; 105: panner, Haas and both reverbs per item, mst_fx_panner_items / mst_fx_haas_items / mst_fx_convolve_items (+ its prepare, table and workspace queries) / mst_fx_algorithmic_reverb_items; 104: mst_tcn_set_fusion / mst_tcn_get_fusion; 103: per-item FX parameters, mst_fx_biquad_cascade_items / mst_fx_compressor_items / mst_fx_midside_imager_items / mst_fx_gain_items; 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
+int mst_version(void);          /* 111: mst_ntxent_forward / mst_ntxent_backward / mst_rms_loss_forward / mst_rms_loss_backward and their workspace queries; 110: mst_tcn_set_chunk / mst_tcn_get_chunk; 109: mst_mss_backward / mst_mss_backward_workspace_bytes; 108: mst_batch_gather_pcm / mst_batch_finish; 107: mst_tcn_context; 106: mst_mixfeat_spectral; 105: panner, Haas and both reverbs per item, mst_fx_panner_items / mst_fx_haas_items / mst_fx_convolve_items (+ its prepare, table and workspace queries) / mst_fx_algorithmic_reverb_items; 104: mst_tcn_set_fusion / mst_tcn_get_fusion; 103: per-item FX parameters, mst_fx_biquad_cascade_items / mst_fx_compressor_items / mst_fx_midside_imager_items / mst_fx_gain_items; 102: the diagnostic plan queries mst_fx_biquad_plan / mst_fx_compressor_plan; 101: the mst_resample_* entry points */
 const char *mst_last_error(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -736,6 +736,41 @@ int mst_batch_gather_pcm(const void *bank_dev, long n_bank_frames, int width, co
  * with torch.clamp's semantics (NaN stays NaN, -0.0 stays -0.0); 0 <= rows[r] < n, 0 <= start[r], start[r] + len <= Lp.  Not in place. */
 int mst_batch_finish(const float *x_dev, int n, long Lp, int C, const long *rows_dev, const long *rows_host, const long *start_dev,
                      const long *start_host, int m, long len, float *out_dev, void *stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Contrastive and gain training losses (csrc/contrast_kernels.h; modules/loss.py: NT_Xent :24-71, RMSLoss :77-93, infoNCE :228-238), value
+ * and gradient.  Since mst_version() 111.  a_dev [n_a, D] and b_dev [n_b, D] fp32 are the two views; every row is divided by
+ * max(|row|, eps) (the norm summed in float64), S = rows . rows * inv_tau on the exact-fp32 MFMA in k order, and
+ *   mode 0  NT-Xent over cat(a, b), N = n_a + n_b rows: loss = (1 / N) sum_i [-S_i,p(i) + log sum_{j != i} exp S_ij], p(i) = i +- N / 2;
+ *   mode 1  infoNCE: S = A B^T * inv_tau, loss = mean cross-entropy of row i against label i, no masked diagonal.
+ * Max subtraction, exp, log and every sum over a row or over the rows in float64 in a fixed order; no atomics: the same inputs give the
+ * same bits in every run.  loss_dev is one float64.  fp32 operands only - there is no bf16 mode.
+ * The forward-only call writes no G and runs no gradient kernel; it leaves S, the normalised rows and the norms in its workspace.  The
+ * backward either takes that workspace back (ws_from_forward = 1: the SAME operands, sizes and mode, the buffer untouched since the forward
+ * and handed over ONCE - the backward writes G over S) or recomputes S from a_dev and b_dev (ws_from_forward = 0: any workspace of the
+ * size).  Both give the same bits.  G = (softmax - one-hot) * dloss / rows over S in place, dZh = (G + G^T) Zh * inv_tau (mode 1: dA = G B,
+ * dB = G^T A) on the same MFMA, then each row through its normalisation.  dloss_dev is one float64 read on the device (no host synchronisation);
+ * grad_a_dev [n_a, D] and grad_b_dev [n_b, D] are written, not accumulated.  A row whose norm is below eps has similarity 0 to everything
+ * and gets a gradient of exact zeros.
+ * Limits (MST_ERR_UNSUPPORTED, the message names the number): n_a == n_b, n_a + n_b <= 4096 (even in mode 0 by construction), D <= 8192.
+ * The workspace holds S (N^2 fp32), the normalised rows (N D fp32) and 3 N scalars; with_grad asks no more (G overwrites S).
+ * ---------------------------------------------------------------------------------------------- */
+size_t mst_ntxent_workspace_bytes(int n_a, int n_b, int D, int with_grad);
+int mst_ntxent_forward(const float *a_dev, const float *b_dev, int n_a, int n_b, int D, double inv_tau, double eps, int mode,
+                       double *loss_dev, void *workspace, size_t workspace_bytes, void *stream);
+int mst_ntxent_backward(const float *a_dev, const float *b_dev, int n_a, int n_b, int D, double inv_tau, double eps, int mode,
+                        const double *dloss_dev, float *grad_a_dev, float *grad_b_dev, int ws_from_forward, void *workspace,
+                        size_t workspace_bytes, void *stream);
+/* RMSLoss: est_dev, tgt_dev fp32 [rows, T] (the reference's [B, C, T] with rows = B C).  Per row rms = sqrt(mean x^2) from a float64 sum of
+ * squares in a fixed order; w = weight_factor * max(|rms_t - rms_e|, 1 / weight_factor); loss = mean_r(w^1.5) * mean_r((rms_e - rms_t)^2) -
+ * nn.MSELoss(reduce=None) is the MEAN reduction.  loss_dev is one float64.  The backward recomputes the sums and writes
+ * grad_est_dev[r, t] = c_r est[r, t], c_r formed on the device from the row sums and dloss_dev (one float64); a row of est without energy
+ * gets exact zeros, and |rms_t - rms_e| < 1 / weight_factor passes no gradient through w (torch.clamp).  rows <= 65535, T < 2^30. */
+size_t mst_rms_loss_workspace_bytes(int rows, long T);
+int mst_rms_loss_forward(const float *est_dev, const float *tgt_dev, int rows, long T, double weight_factor, double *loss_dev,
+                         void *workspace, size_t workspace_bytes, void *stream);
+int mst_rms_loss_backward(const float *est_dev, const float *tgt_dev, int rows, long T, double weight_factor, const double *dloss_dev,
+                          float *grad_est_dev, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -218,6 +218,12 @@ SIGNATURES = {
     "mst_fx_convolve": (C.c_int, [_P, _F, _F, C.c_long, _F, C.c_long, C.c_double, C.c_double, _P, C.c_size_t, _P]),
     "mst_batch_gather_pcm": (C.c_int, [_P, C.c_long, C.c_int, _P, _P, C.c_int, C.c_long, _F, _P]),
     "mst_batch_finish": (C.c_int, [_F, C.c_int, C.c_long, C.c_int, _P, _P, _P, _P, C.c_int, C.c_long, _F, _P]),
+    "mst_ntxent_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mst_ntxent_forward": (C.c_int, [_F, _F, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _P, _P, C.c_size_t, _P]),
+    "mst_ntxent_backward": (C.c_int, [_F, _F, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _P, _F, _F, C.c_int, _P, C.c_size_t, _P]),
+    "mst_rms_loss_workspace_bytes": (C.c_size_t, [C.c_int, C.c_long]),
+    "mst_rms_loss_forward": (C.c_int, [_F, _F, C.c_int, C.c_long, C.c_double, _P, _P, C.c_size_t, _P]),
+    "mst_rms_loss_backward": (C.c_int, [_F, _F, C.c_int, C.c_long, C.c_double, _P, _F, _P, C.c_size_t, _P]),
 }
 
 

@@ -13,5 +13,5 @@ int mst_fail(int code, const std::string &msg) {
     return code;
 }
 
-extern "C" int mst_version(void) { return 110; }
+extern "C" int mst_version(void) { return 111; }
 extern "C" const char *mst_last_error(void) { return g_err.c_str(); }

@@ -5,6 +5,7 @@
 #include "fft_kernels.h"
 #include "fx_kernels.h"
 #include "mss_kernels.h"
+#include "contrast_kernels.h"
 #include "mixfeat_kernels.h"
 #include "resample_kernels.h"
 #include "batch_kernels.h"
@@ -1747,6 +1748,164 @@ extern "C" int mst_mss_spectrogram(MstMss *h, int scale, const float *x, int B, 
     int rc;
     if ((rc = mss_check_length(h, scale, scale, B, L, "mst_mss_spectrogram"))) return rc;
     return mss_launch<MSS_EPI_MAG>(h, scale, x, C == 2 ? x + L : nullptr, (long)C * L, B, 1, L, 0, nullptr, mag, C, stream);
+}
+
+// ---- contrastive and gain training losses (csrc/contrast_kernels.h) ---------------------------------------------------------------------
+namespace {
+struct NtxPlan {
+    int N, M, Nc;                   // rows of cat(a, b); rows and columns of S (mode 0: N x N, mode 1: n_a x n_b)
+    double *rowterm;                // [N] float64
+    float *S, *zh, *invn;           // [M, Nc], [N, D], [2, N]
+};
+size_t ntx_bytes(int n_a, int n_b, int D) {
+    const size_t N = (size_t)n_a + (size_t)n_b;
+    return 256 + align_up(N * sizeof(double), 256) + align_up(N * N * sizeof(float), 256) + align_up(N * (size_t)D * sizeof(float), 256) +
+           align_up(2 * N * sizeof(float), 256);
+}
+int ntx_check(const char *who, const float *a, const float *b, int n_a, int n_b, int D, double inv_tau, double eps, int mode, const void *ws,
+              size_t ws_bytes, NtxPlan &p) {
+    if (!a || !b || n_a < 1 || n_b < 1 || D < 1 || !(inv_tau > 0.0) || !(eps >= 0.0) || (mode != 0 && mode != 1))
+        return fail(MST_ERR_ARG, std::string(who) + ": bad argument");
+    if (n_a != n_b)
+        return fail(MST_ERR_UNSUPPORTED, std::string(who) + ": n_a = " + std::to_string(n_a) + ", n_b = " + std::to_string(n_b) + " (the two views must have as many rows)");
+    const long N = (long)n_a + n_b;
+    if (N > 4096) return fail(MST_ERR_UNSUPPORTED, std::string(who) + ": N = " + std::to_string(N) + " rows (at most 4096)");
+    if (mode == 0 && (N & 1)) return fail(MST_ERR_UNSUPPORTED, std::string(who) + ": N = " + std::to_string(N) + " rows (NT-Xent pairs row i with row i + N / 2: N must be even)");
+    if (D > 8192) return fail(MST_ERR_UNSUPPORTED, std::string(who) + ": D = " + std::to_string(D) + " (at most 8192)");
+    if (!ws || ws_bytes < ntx_bytes(n_a, n_b, D)) return fail(MST_ERR_WORKSPACE, std::string(who) + ": workspace null or too small");
+    p.N = (int)N;
+    p.M = mode == 0 ? (int)N : n_a;
+    p.Nc = mode == 0 ? (int)N : n_b;
+    unsigned char *q = (unsigned char *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    p.rowterm = (double *)q;
+    q += align_up((size_t)N * sizeof(double), 256);
+    p.S = (float *)q;
+    q += align_up((size_t)N * N * sizeof(float), 256);
+    p.zh = (float *)q;
+    q += align_up((size_t)N * D * sizeof(float), 256);
+    p.invn = (float *)q;
+    return MST_OK;
+}
+// normalise and S (skipped when the workspace still holds a forward's), then per row: `dloss` null the loss terms, otherwise G in place of S
+int ntx_front(const NtxPlan &p, const float *a, const float *b, int n_a, int D, double inv_tau, double eps, int mode, const double *dloss,
+              bool have_s, void *stream) {
+    if (!have_s) {
+        MST_LAUNCH(ntx_normalize_kernel, dim3((unsigned)p.N), dim3(NTX_THREADS), stream, a, b, n_a, p.N, D, eps, p.zh, p.invn);
+        MST_CHECK_LAUNCH("ntx_normalize_kernel");
+        const float *Y = mode == 0 ? p.zh : p.zh + (size_t)n_a * D;
+        MST_LAUNCH(ntx_gram_kernel, dim3((unsigned)((p.M + NTX_TILE - 1) / NTX_TILE), (unsigned)((p.Nc + NTX_COLS - 1) / NTX_COLS)), dim3(NTX_THREADS), stream,
+                   (const float *)p.zh, Y, p.M, p.Nc, D, (float)inv_tau, p.S);
+        MST_CHECK_LAUNCH("ntx_gram_kernel");
+    }
+    MST_LAUNCH(ntx_rows_kernel, dim3((unsigned)p.M), dim3(NTX_THREADS), stream, p.S, p.M, p.Nc, mode == 0 ? 1 : 0, mode == 0 ? p.N / 2 : 0, dloss,
+               p.rowterm);
+    MST_CHECK_LAUNCH("ntx_rows_kernel");
+    return MST_OK;
+}
+}  // namespace
+
+extern "C" size_t mst_ntxent_workspace_bytes(int n_a, int n_b, int D, int with_grad) {
+    (void)with_grad;      // the backward writes G over S: it needs no more than the forward
+    if (n_a < 1 || n_b < 1 || D < 1 || (long)n_a + n_b > 4096 || D > 8192) return 0;
+    return ntx_bytes(n_a, n_b, D);
+}
+
+extern "C" int mst_ntxent_forward(const float *a, const float *b, int n_a, int n_b, int D, double inv_tau, double eps, int mode, double *loss,
+                                  void *ws, size_t ws_bytes, void *stream) {
+    NtxPlan p;
+    int rc;
+    if (!loss) return fail(MST_ERR_ARG, "mst_ntxent_forward: bad argument");
+    if ((rc = ntx_check("mst_ntxent_forward", a, b, n_a, n_b, D, inv_tau, eps, mode, ws, ws_bytes, p))) return rc;
+    if ((rc = ntx_front(p, a, b, n_a, D, inv_tau, eps, mode, nullptr, false, stream))) return rc;
+    MST_LAUNCH(ntx_mean_kernel, dim3(1), dim3(NTX_THREADS), stream, (const double *)p.rowterm, p.M, loss);
+    MST_CHECK_LAUNCH("ntx_mean_kernel");
+    return MST_OK;
+}
+
+extern "C" int mst_ntxent_backward(const float *a, const float *b, int n_a, int n_b, int D, double inv_tau, double eps, int mode,
+                                   const double *dloss, float *grad_a, float *grad_b, int ws_from_forward, void *ws, size_t ws_bytes,
+                                   void *stream) {
+    NtxPlan p;
+    int rc;
+    if (!dloss || !grad_a || !grad_b || grad_a == grad_b) return fail(MST_ERR_ARG, "mst_ntxent_backward: bad argument");
+    if ((rc = ntx_check("mst_ntxent_backward", a, b, n_a, n_b, D, inv_tau, eps, mode, ws, ws_bytes, p))) return rc;
+    if ((rc = ntx_front(p, a, b, n_a, D, inv_tau, eps, mode, dloss, ws_from_forward != 0, stream))) return rc;
+    const unsigned gy = (unsigned)((D + NTX_COLS - 1) / NTX_COLS);
+    if (mode == 0) {
+        MST_LAUNCH(ntx_grad_kernel, dim3((unsigned)((p.N + NTX_TILE - 1) / NTX_TILE), gy), dim3(NTX_THREADS), stream, (const float *)p.S, p.N, p.N, p.N, 1, 1,
+                   (const float *)p.zh, D, (float)inv_tau, grad_a, grad_b, n_a);
+        MST_CHECK_LAUNCH("ntx_grad_kernel");
+    } else {
+        const dim3 grid((unsigned)((n_a + NTX_TILE - 1) / NTX_TILE), gy);
+        MST_LAUNCH(ntx_grad_kernel, grid, dim3(NTX_THREADS), stream, (const float *)p.S, n_a, n_b, n_b, 1, 0, (const float *)(p.zh + (size_t)n_a * D), D,
+                   (float)inv_tau, grad_a, grad_a, n_a);
+        MST_CHECK_LAUNCH("ntx_grad_kernel");
+        MST_LAUNCH(ntx_grad_kernel, grid, dim3(NTX_THREADS), stream, (const float *)p.S, n_b, n_a, n_b, 0, 1, (const float *)p.zh, D, (float)inv_tau, grad_b,
+                   grad_b, n_b);
+        MST_CHECK_LAUNCH("ntx_grad_kernel");
+    }
+    MST_LAUNCH(ntx_project_kernel, dim3((unsigned)p.N), dim3(NTX_THREADS), stream, grad_a, grad_b, n_a, (const float *)p.zh, (const float *)(p.invn + p.N), D);
+    MST_CHECK_LAUNCH("ntx_project_kernel");
+    return MST_OK;
+}
+
+namespace {
+struct RmsPlan {
+    int nchunks;
+    double *partial, *coef, *rms;      // [2, rows, nchunks], [rows], [2, rows]
+};
+size_t rms_bytes(int rows, long T) {
+    const size_t nchunks = (size_t)((T + RMS_CHUNK - 1) / RMS_CHUNK);
+    return 256 + align_up(2 * (size_t)rows * nchunks * sizeof(double), 256) + align_up((size_t)rows * sizeof(double), 256) +
+           align_up(2 * (size_t)rows * sizeof(double), 256);
+}
+int rms_check(const char *who, const float *est, const float *tgt, int rows, long T, double wf, const void *ws, size_t ws_bytes, RmsPlan &p) {
+    if (!est || !tgt || rows < 1 || T < 1 || !(wf > 0.0)) return fail(MST_ERR_ARG, std::string(who) + ": bad argument");
+    if (rows > 65535) return fail(MST_ERR_UNSUPPORTED, std::string(who) + ": rows = " + std::to_string(rows) + " (at most 65535 rows per call)");
+    if (T >= (1L << 30)) return fail(MST_ERR_UNSUPPORTED, std::string(who) + ": T = " + std::to_string(T) + " (below 2^30)");
+    if (!ws || ws_bytes < rms_bytes(rows, T)) return fail(MST_ERR_WORKSPACE, std::string(who) + ": workspace null or too small");
+    p.nchunks = (int)((T + RMS_CHUNK - 1) / RMS_CHUNK);
+    unsigned char *q = (unsigned char *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    p.partial = (double *)q;
+    q += align_up(2 * (size_t)rows * p.nchunks * sizeof(double), 256);
+    p.coef = (double *)q;
+    q += align_up((size_t)rows * sizeof(double), 256);
+    p.rms = (double *)q;
+    return MST_OK;
+}
+int rms_front(const RmsPlan &p, const float *est, const float *tgt, int rows, long T, double wf, const double *dloss, double *loss, void *stream) {
+    MST_LAUNCH(rms_rows_kernel, dim3((unsigned)p.nchunks, (unsigned)rows, 2u), dim3(NTX_THREADS), stream, est, tgt, T, p.nchunks, p.partial);
+    MST_CHECK_LAUNCH("rms_rows_kernel");
+    MST_LAUNCH(rms_finish_kernel, dim3(1), dim3(NTX_THREADS), stream, (const double *)p.partial, rows, p.nchunks, T, wf, dloss, loss, p.coef, p.rms);
+    MST_CHECK_LAUNCH("rms_finish_kernel");
+    return MST_OK;
+}
+}  // namespace
+
+extern "C" size_t mst_rms_loss_workspace_bytes(int rows, long T) {
+    if (rows < 1 || rows > 65535 || T < 1 || T >= (1L << 30)) return 0;
+    return rms_bytes(rows, T);
+}
+
+extern "C" int mst_rms_loss_forward(const float *est, const float *tgt, int rows, long T, double weight_factor, double *loss, void *ws,
+                                    size_t ws_bytes, void *stream) {
+    RmsPlan p;
+    int rc;
+    if (!loss) return fail(MST_ERR_ARG, "mst_rms_loss_forward: bad argument");
+    if ((rc = rms_check("mst_rms_loss_forward", est, tgt, rows, T, weight_factor, ws, ws_bytes, p))) return rc;
+    return rms_front(p, est, tgt, rows, T, weight_factor, nullptr, loss, stream);
+}
+
+extern "C" int mst_rms_loss_backward(const float *est, const float *tgt, int rows, long T, double weight_factor, const double *dloss,
+                                     float *grad_est, void *ws, size_t ws_bytes, void *stream) {
+    RmsPlan p;
+    int rc;
+    if (!dloss || !grad_est) return fail(MST_ERR_ARG, "mst_rms_loss_backward: bad argument");
+    if ((rc = rms_check("mst_rms_loss_backward", est, tgt, rows, T, weight_factor, ws, ws_bytes, p))) return rc;
+    if ((rc = rms_front(p, est, tgt, rows, T, weight_factor, dloss, nullptr, stream))) return rc;
+    MST_LAUNCH(rms_grad_kernel, dim3((unsigned)p.nchunks, (unsigned)rows), dim3(NTX_THREADS), stream, est, (const double *)p.coef, T, grad_est);
+    MST_CHECK_LAUNCH("rms_grad_kernel");
+    return MST_OK;
 }
 
 // ---- mixing-feature metrics (csrc/mixfeat_kernels.h) -----------------------------------------------------------------------
