@@ -686,11 +686,75 @@ struct CompArgs {
     double *out_ms = nullptr;      // stereo: the apply pass also adds sum((l + r)^2), sum((l - r)^2) per item to [item][MST_SUMSQ_SLOTS][2] (for the imager)
 };
 
-__global__ __launch_bounds__(256) void fx_compressor_kernel(CompArgs a) {
+// the time-parallel smoother's arguments (the section "The smoother, parallel in time" below explains them)
+#define MST_COMP_T 32                      // steps per chunk: T + 1 pieces
+#define MST_COMP_NP (MST_COMP_T + 1)
+#define MST_COMP_REC (MST_COMP_NP + 1)   // doubles per stored record: b_0, lb_1 .. lb_T (NEVER beyond the chunk's pieces), one pad
+#define MST_COMP_NEVER 1e300
+
+struct CompMapArgs {
+    const double *log_tab; // fx_log10_table_kernel's 256 doubles
+    double *maps;         // [n_seq][nchunks][MST_COMP_REC]  b_0, lb_1 .. lb_T per chunk
+    double *ystart;       // [nchunks][n_seq]  smoother value at the start of each chunk
+    int n_seq, nchunks;
+    long L;
+    double aA, aR;        // attack / release coefficients alpha
+    int use_min;          // aA > aR: concave maps
+    // slope of the piece at sorted position p and its reciprocal; [0]: a chunk of T steps, [1]: the last chunk when it is shorter
+    // (0 beyond its pieces)
+    double slope[2][MST_COMP_NP], inv_slope[2][MST_COMP_NP];
+    // time slices (the host pipelines map -> chain -> apply over slices of whole batches, mst_api.hip compressor_run): the map launch covers
+    // chunks chunk0 .. chunk0 + gridDim.x - 1, the chain launch batches batch0 .. batch1 - 1 (of MST_CHAIN_CB chunks); a chain launch with
+    // batch0 > 0 starts from ycarry[seq] (what the launch before it left there) instead of yL_prev = 0, and every launch leaves its last value
+    int chunk0 = 0, batch0 = 0, batch1 = 0;
+    double *ycarry = nullptr;      // [n_seq]
+};
+#define MST_CHAIN_CB 32                    // chunks per batch of the chain kernel
+
+// the table of mst_fx_compressor_items (filled on the host by mst_fx_compressor_items_prepare with the shared call's own functions)
+struct FxiCmpTab {
+    const double *aA, *aR;        // [n_items] attack / release coefficients
+    const double *slope, *inv;    // [n_items][2][MST_COMP_NP]: CompMapArgs::slope / inv_slope of the item
+    int C;
+};
+
+// Every pass that meets a time constant is ONE body, fxb_comp_*, under two kernels: fx_* for mst_fx_compressor / _grid and fxi_cmp_* for
+// mst_fx_compressor_items.  The body asks its policy TC - and nothing else differs between the two forms - for the attack / release
+// coefficient of an item, the slope and inverse-slope rows of a sequence's item (which = 0: a chunk of T steps, 1: the short last chunk),
+// threshold / ratio of an item in the serial kernel, and whether the chunk maps take min or max.  Threshold and ratio per item reach the
+// other passes as CompArgs::thr_items / ratio_items like the parameter grid's (fx_comp_curve); fx_comp_gain_kernel and
+// fx_comp_apply_kernel<false> never see a time constant and serve both forms as they are.  tests/test_fx_items_*.py hold item i of the
+// per-item call to the bits of the shared call with item i's settings.
+template <bool USE_MIN = false>
+struct FxCompCall {      // time constants shared by the call: kernel arguments.  USE_MIN matters to the map kernel alone
+    __device__ __forceinline__ double thr(const CompArgs &a, int) const { return a.threshold; }
+    __device__ __forceinline__ double ratio(const CompArgs &a, int) const { return a.ratio; }
+    __device__ __forceinline__ double att(const CompArgs &a, int) const { return a.alpha_att; }
+    __device__ __forceinline__ double rel(const CompArgs &a, int) const { return a.alpha_rel; }
+    __device__ __forceinline__ double att(const CompMapArgs &a, int) const { return a.aA; }
+    __device__ __forceinline__ double rel(const CompMapArgs &a, int) const { return a.aR; }
+    __device__ __forceinline__ const double *slope(const CompMapArgs &a, int, int which) const { return a.slope[which]; }
+    __device__ __forceinline__ const double *inv_slope(const CompMapArgs &a, int, int which) const { return a.inv_slope[which]; }
+    __device__ __forceinline__ bool use_min(double, double) const { return USE_MIN; }      // a constant of the instantiation
+};
+struct FxCompItems {     // time constants per item: the prepared table
+    FxiCmpTab t;
+    __device__ __forceinline__ double thr(const CompArgs &a, int item) const { return a.thr_items[item]; }
+    __device__ __forceinline__ double ratio(const CompArgs &a, int item) const { return a.ratio_items[item]; }
+    template <class A> __device__ __forceinline__ double att(const A &, int item) const { return t.aA[item]; }
+    template <class A> __device__ __forceinline__ double rel(const A &, int item) const { return t.aR[item]; }
+    __device__ __forceinline__ const double *slope(const CompMapArgs &, int seq, int which) const { return t.slope + ((size_t)(seq / t.C) * 2 + which) * MST_COMP_NP; }
+    __device__ __forceinline__ const double *inv_slope(const CompMapArgs &, int seq, int which) const { return t.inv + ((size_t)(seq / t.C) * 2 + which) * MST_COMP_NP; }
+    __device__ __forceinline__ bool use_min(double aA, double aR) const { return aA > aR; }      // convex and concave items share a wave: a select per lane
+};
+
+template <class TC>
+__device__ __forceinline__ void fxb_comp_serial(const CompArgs a, const TC tc) {
     const int lane = threadIdx.x & 63;
     const int seq = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (seq >= a.n_seq) return;   // wave-uniform
     const int item = seq / a.C, c = seq % a.C;
+    const double thr = tc.thr(a, item), ratio = tc.ratio(a, item), aatt = tc.att(a, item), arel = tc.rel(a, item);
     const float *xp = a.x + (size_t)item * a.L * a.C + c;
     float *yp = a.y + (size_t)item * a.L * a.C + c;
     double prev = 0.0;            // yL_prev is forced to 0 on entry (:553)
@@ -700,24 +764,26 @@ __global__ __launch_bounds__(256) void fx_compressor_kernel(CompArgs a) {
         const double ax = fabs(xv);
         const double xg = (ax < 0.000001) ? -120.0 : 20.0 * log10(ax);
         double yg = 0.0;          // ratio == 1: neither branch assigns y_g (:564-573)
-        if (a.ratio > 1.0)
-            yg = (xg >= a.threshold) ? a.threshold + (xg - a.threshold) / a.ratio : xg;
-        else if (a.ratio < 1.0)
-            yg = (xg <= a.threshold) ? a.threshold + (xg - a.threshold) / (1.0 / a.ratio) : xg;
+        if (ratio > 1.0)
+            yg = (xg >= thr) ? thr + (xg - thr) / ratio : xg;
+        else if (ratio < 1.0)
+            yg = (xg <= thr) ? thr + (xg - thr) / (1.0 / ratio) : xg;
         const double xl = xg - yg;
         double yl = 0.0;
         const int cnt = (a.L - n0) < 64 ? (int)(a.L - n0) : 64;
         for (int i = 0; i < cnt; ++i) {
             const double v = __shfl(xl, i);
             if (v > prev)
-                prev = a.alpha_att * prev + (1.0 - a.alpha_att) * v;
+                prev = aatt * prev + (1.0 - aatt) * v;
             else
-                prev = a.alpha_rel * prev + (1.0 - a.alpha_rel) * v;
+                prev = arel * prev + (1.0 - arel) * v;
             if (lane == i) yl = prev;
         }
         if (n < a.L) yp[n * a.C] = (float)(xv * pow(10.0, (a.makeup - yl) / 20.0));
     }
 }
+__global__ __launch_bounds__(256) void fx_compressor_kernel(CompArgs a) { fxb_comp_serial(a, FxCompCall<>{}); }
+__global__ __launch_bounds__(256) void fxi_cmp_serial_kernel(CompArgs a, FxiCmpTab tb) { fxb_comp_serial(a, FxCompItems{tb}); }
 
 // ------------------------------------------------------------------------------------------------
 // The same compressor split by dependency structure, for signals too short for the time-parallel form below (fewer than four
@@ -824,7 +890,8 @@ __global__ __launch_bounds__(256) void fx_comp_gain_kernel(CompArgs a, double *x
     }
 }
 
-__global__ __launch_bounds__(64) void fx_comp_smooth_kernel(CompArgs a, double *xl) {
+template <class TC>
+__device__ __forceinline__ void fxb_comp_smooth(const CompArgs a, double *xl, const TC tc) {
     const int seq = blockIdx.x * 64 + threadIdx.x;
     const bool live = seq < a.n_seq;
     // y <- alpha y + (1 - alpha) x, alpha = attack coefficient when x > y else release, evaluated as y + c (x - y) with
@@ -836,7 +903,8 @@ __global__ __launch_bounds__(64) void fx_comp_smooth_kernel(CompArgs a, double *
     unsigned char *base = (unsigned char *)xl;
     const unsigned row = (unsigned)a.n_seq * 8u;                       // bytes per time step
     const unsigned off0 = (unsigned)(live ? seq : a.n_seq - 1) * 8u;   // idle lanes of the last wave shadow a live one, store nothing
-    const double ca = 1.0 - a.alpha_att, cr = 1.0 - a.alpha_rel;
+    const int item = (live ? seq : a.n_seq - 1) / a.C;
+    const double ca = 1.0 - tc.att(a, item), cr = 1.0 - tc.rel(a, item);
     double prev = 0.0;
     constexpr int NB = 16;
     const long nfull = a.L / NB;
@@ -870,6 +938,8 @@ __global__ __launch_bounds__(64) void fx_comp_smooth_kernel(CompArgs a, double *
         if (live) *q = prev;
     }
 }
+__global__ __launch_bounds__(64) void fx_comp_smooth_kernel(CompArgs a, double *xl) { fxb_comp_smooth(a, xl, FxCompCall<>{}); }
+__global__ __launch_bounds__(64) void fxi_cmp_smooth_kernel(CompArgs a, double *xl, FxiCmpTab tb) { fxb_comp_smooth(a, xl, FxCompItems{tb}); }
 
 // ------------------------------------------------------------------------------------------------
 // The smoother, parallel in time.  One step is y <- f_x(y) = (x > y) ? aA y + cA x : aR y + cR x.  With aA <= aR (attack faster
@@ -893,34 +963,11 @@ __global__ __launch_bounds__(64) void fx_comp_smooth_kernel(CompArgs a, double *
 // new_s = max(g_(s-1), min(g_s, x)): five float64 operations per piece and step, no compare, no select, no data-dependent move.
 // (Round 2's first version kept (a, b, lb) per piece and shifted them under exec masks: 4x the instructions, 2.5x the time.)
 // ------------------------------------------------------------------------------------------------
-#define MST_COMP_T 32                      // steps per chunk: T + 1 pieces
-#define MST_COMP_NP (MST_COMP_T + 1)
-#define MST_COMP_REC (MST_COMP_NP + 1)   // doubles per stored record: b_0, lb_1 .. lb_T (NEVER beyond the chunk's pieces), one pad
-#define MST_COMP_NEVER 1e300
 
-struct CompMapArgs {
-    const double *log_tab; // fx_log10_table_kernel's 256 doubles
-    double *maps;         // [n_seq][nchunks][MST_COMP_REC]  b_0, lb_1 .. lb_T per chunk
-    double *ystart;       // [nchunks][n_seq]  smoother value at the start of each chunk
-    int n_seq, nchunks;
-    long L;
-    double aA, aR;        // attack / release coefficients alpha
-    int use_min;          // aA > aR: concave maps
-    // slope of the piece at sorted position p and its reciprocal; [0]: a chunk of T steps, [1]: the last chunk when it is shorter
-    // (0 beyond its pieces)
-    double slope[2][MST_COMP_NP], inv_slope[2][MST_COMP_NP];
-    // time slices (the host pipelines map -> chain -> apply over slices of whole batches, mst_api.hip compressor_run): the map launch covers
-    // chunks chunk0 .. chunk0 + gridDim.x - 1, the chain launch batches batch0 .. batch1 - 1 (of MST_CHAIN_CB chunks); a chain launch with
-    // batch0 > 0 starts from ycarry[seq] (what the launch before it left there) instead of yL_prev = 0, and every launch leaves its last value
-    int chunk0 = 0, batch0 = 0, batch1 = 0;
-    double *ycarry = nullptr;      // [n_seq]
-};
-#define MST_CHAIN_CB 32                    // chunks per batch of the chain kernel
-
-// grid (nchunks, ceil(n_seq / 64)), 64 threads: lanes = sequences of one chunk (coalesced time-major loads).  Four waves per SIMD
-// (<= 128 registers, 8.5 KB of LDS): the early steps of a chunk have few pieces and little to overlap within one wave.
-template <bool USE_MIN>
-__global__ __launch_bounds__(64) MST_WAVES_PER_SIMD(4) MST_HEAVY_UNROLL void fx_comp_map_kernel(CompMapArgs a, CompArgs ca) {
+// grid (nchunks, ceil(n_seq / 64)), 64 threads: lanes = sequences of one chunk (coalesced time-major loads).  The shared kernel: four
+// waves per SIMD (<= 128 registers, 8.5 KB of LDS): the early steps of a chunk have few pieces and little to overlap within one wave.
+template <class TC>
+__device__ __forceinline__ void fxb_comp_map(const CompMapArgs a, const CompArgs ca, const TC tc) {
     constexpr int PASS = 16;                                        // doubles of every record that cross the LDS tile at a time (128 B)
     __shared__ double tr[64 * (PASS + 1)];
     __shared__ double tab[256];
@@ -928,12 +975,13 @@ __global__ __launch_bounds__(64) MST_WAVES_PER_SIMD(4) MST_HEAVY_UNROLL void fx_
     const int seq = blockIdx.y * 64 + threadIdx.x;
     const bool live = seq < a.n_seq;
     const size_t sq = live ? seq : a.n_seq - 1;
-    const double cA = 1.0 - a.aA, cR = 1.0 - a.aR;
     // the level differences x_l are computed here from the audio (a lane walks its own sequence: 32 frames = 256 contiguous bytes that
     // it shares with the lane of the other channel), not read from a float64 scratch that a separate pass would have to write
     for (int i = threadIdx.x; i < 256; i += 64) tab[i] = a.log_tab[i];
     const int item = (int)(sq / ca.C);
     const FxCompCurve cv = fx_comp_curve(ca, item);
+    const double aA = tc.att(a, item), aR = tc.rel(a, item), cA = 1.0 - aA, cR = 1.0 - aR;
+    const bool use_min = tc.use_min(aA, aR);
     const float *xp = ca.x + ((size_t)(ca.shared_x ? 0 : item) * ca.L) * ca.C + sq % ca.C;
     __builtin_amdgcn_wave_barrier();
     double lb[MST_COMP_NP + 1];                                     // lb[1 .. t]: the values at which the pieces meet after t steps
@@ -944,15 +992,15 @@ __global__ __launch_bounds__(64) MST_WAVES_PER_SIMD(4) MST_HEAVY_UNROLL void fx_
         if (n < a.L) {                                              // uniform over the wave
             const double x = fx_comp_level_diff(xp[(size_t)n * ca.C] * cv.sf, cv.thr, cv.mul, cv.mode, tab);
             const double oA = cA * x, oR = cR * x;
-            b0 = fma(a.aA, b0, oA);
+            b0 = fma(aA, b0, oA);
             // downwards, in place: slot s reads the old slots s and s - 1.  g = f_x(old value) = max (convex) / min (concave) of the branches
             double m = x;                                           // min(g_s, x); above the top piece: x
 #pragma unroll
             for (int s = t + 1; s >= 1; --s) {
                 if (s > 1) {
                     const double v = lb[s - 1];
-                    const double gA = fma(a.aA, v, oA), gR = fma(a.aR, v, oR);
-                    const double g = USE_MIN ? fmin(gA, gR) : fmax(gA, gR);
+                    const double gA = fma(aA, v, oA), gR = fma(aR, v, oR);
+                    const double g = use_min ? fmin(gA, gR) : fmax(gA, gR);
                     lb[s] = fmax(g, m);
                     m = fmin(g, x);
                 } else {
@@ -986,6 +1034,9 @@ __global__ __launch_bounds__(64) MST_WAVES_PER_SIMD(4) MST_HEAVY_UNROLL void fx_
     pass(std::integral_constant<int, 1>{});
     pass(std::integral_constant<int, 2>{});
 }
+template <bool USE_MIN>
+__global__ __launch_bounds__(64) MST_WAVES_PER_SIMD(4) MST_HEAVY_UNROLL void fx_comp_map_kernel(CompMapArgs a, CompArgs ca) { fxb_comp_map(a, ca, FxCompCall<USE_MIN>{}); }
+__global__ __launch_bounds__(64) MST_HEAVY_UNROLL void fxi_cmp_map_kernel(CompMapArgs a, CompArgs ca, FxiCmpTab tb) { fxb_comp_map(a, ca, FxCompItems{tb}); }
 
 // grid n_seq, 384 threads: six waves per sequence.  Wave 0 walks the chunks (lanes = pieces); waves 1, 2, 3 and 5 run one batch of CB
 // chunks ahead of it (a quarter of a batch each; with two of them the walker waited for its entries: 202 us against 153 alone; wave 4
@@ -1000,7 +1051,8 @@ __global__ __launch_bounds__(64) MST_WAVES_PER_SIMD(4) MST_HEAVY_UNROLL void fx_
 // register (v_writelane) and stored once per batch.
 #define MST_CHAIN_HELPERS 4
 #define MST_CHAIN_THREADS 384
-__global__ __launch_bounds__(MST_CHAIN_THREADS) void fx_comp_chain_kernel(CompMapArgs a) {
+template <class TC>
+__device__ __forceinline__ void fxb_comp_chain(const CompMapArgs a, const TC tc) {
     constexpr int CB = MST_CHAIN_CB, REC = MST_COMP_REC, NPE = MST_COMP_NP + 1, ENT = 2 * NPE;      // chunks per batch, doubles per record / per chunk of entries
     constexpr int NH = MST_CHAIN_HELPERS, HB = CB / NH;               // helper waves; chunks per helper wave and batch
     constexpr int NLD = (HB * REC / 2 + 63) / 64;                     // 16-byte loads per helper lane per batch
@@ -1010,12 +1062,14 @@ __global__ __launch_bounds__(MST_CHAIN_THREADS) void fx_comp_chain_kernel(CompMa
     static_assert(NH == 4, "helper waves 1, 2, 3, 5");
     const int seq = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hw = wave == 5 ? 3 : (wave > 0 ? wave - 1 : 0);
     const bool helper = wave != 0 && wave != 4;
-    const double2 *m = (const double2 *)(a.maps + (size_t)seq * a.nchunks * REC);
+    const double *sl0 = tc.slope(a, seq, 0), *sl1 = tc.slope(a, seq, 1);      // a workgroup serves one sequence: its item's rows, once
+    const double *is0 = tc.inv_slope(a, seq, 0), *is1 = tc.inv_slope(a, seq, 1);
+    const double2 *m =(const double2 *)(a.maps + (size_t)seq * a.nchunks * REC);
     const size_t total = (size_t)a.nchunks * REC / 2;
     const int nbatch = a.batch1;                                      // this launch walks batches batch0 .. batch1 - 1
     // ---- waves 1, 2: global -> registers -> raw records in LDS -> entries
     const int hp = (lane & 31) + 1;                                   // the piece this helper lane rebuilds (1 .. T)
-    const double sl_full = a.slope[0][hp], isl_full = a.inv_slope[0][hp - 1], sl_last = a.slope[1][hp], isl_last = a.inv_slope[1][hp - 1];
+    const double sl_full = sl0[hp], isl_full = is0[hp - 1], sl_last = sl1[hp], isl_last = is1[hp - 1];
     double rx[NLD], ry[NLD];                                          // (plain doubles: an array of double2 stays in scratch memory)
     auto load = [&](int bt) {
 #pragma unroll
@@ -1067,7 +1121,7 @@ __global__ __launch_bounds__(MST_CHAIN_THREADS) void fx_comp_chain_kernel(CompMa
     // yL_prev = 0 on entry (common_audioeffects.py:553); a later time slice continues from the value the slice before it left
     MstUniformF64 yu = mst_wave_read_u64(a.batch0 > 0 ? a.ycarry[seq] : 0.0, 0);
     const int pl = lane < MST_COMP_NP ? MST_COMP_NP - 1 - lane : MST_COMP_NP;   // descending; lanes without a piece read the "never" entry
-    const double a_full = pl < MST_COMP_NP ? a.slope[0][pl] : 0.0, a_last = pl < MST_COMP_NP ? a.slope[1][pl] : 0.0;
+    const double a_full = pl < MST_COMP_NP ? sl0[pl] : 0.0, a_last = pl < MST_COMP_NP ? sl1[pl] : 0.0;
     for (int bt = a.batch0; bt < nbatch; ++bt) {
         const int cur = (bt - a.batch0) & 1;
         if (helper) {
@@ -1115,6 +1169,8 @@ __global__ __launch_bounds__(MST_CHAIN_THREADS) void fx_comp_chain_kernel(CompMa
         __syncthreads();
     }
 }
+__global__ __launch_bounds__(MST_CHAIN_THREADS) void fx_comp_chain_kernel(CompMapArgs a) { fxb_comp_chain(a, FxCompCall<>{}); }
+__global__ __launch_bounds__(MST_CHAIN_THREADS) void fxi_cmp_chain_kernel(CompMapArgs a, FxiCmpTab tb) { fxb_comp_chain(a, FxCompItems{tb}); }
 
 // grid (ceil(L / 64), ceil(n_seq / 64)), 256 threads.  FILL: the whole tail of the compressor on a 64 x 64 (time x sequence) tile - level
 // differences from the audio (yl = the log10 table), the smoother inside each chunk from its true start value (two chunks per tile, one
@@ -1122,8 +1178,8 @@ __global__ __launch_bounds__(MST_CHAIN_THREADS) void fx_comp_chain_kernel(CompMa
 // Energy sums for the chain fusion leave as per-tile partials (tile_sums[time tile][item][3]: sum y^2 and, for stereo with an imager
 // downstream, sum (l + r)^2, sum (l - r)^2; otherwise [time tile][sequence]), reduced in a fixed order by fx_tile_sums_kernel: the same bits on
 // every run (round 5 added them with float64 atomics from concurrently running launches).
-template <bool FILL>
-__global__ __launch_bounds__(256) void fx_comp_apply_kernel(CompArgs a, const double *yl, const double *ystart, int nchunks, int tile0, double *tile_sums) {
+template <bool FILL, class TC>
+__device__ __forceinline__ void fxb_comp_apply(const CompArgs a, const double *yl, const double *ystart, int nchunks, int tile0, double *tile_sums, const TC tc) {
     __shared__ double t[64][65];
     const long tx = (long)blockIdx.x + tile0;                       // time tile (a launch covers the tiles of one time slice)
     const long n0 = tx * 64;
@@ -1163,7 +1219,7 @@ __global__ __launch_bounds__(256) void fx_comp_apply_kernel(CompArgs a, const do
         const int sl = threadIdx.x & 63, hh = threadIdx.x >> 6;
         const long k = tx * 2 + hh;
         if (hh < 2 && s0 + sl < a.n_seq && k < nchunks) {
-            const double cA = 1.0 - a.alpha_att, cR = 1.0 - a.alpha_rel;
+            const double cA = 1.0 - tc.att(a, (s0 + sl) / a.C), cR = 1.0 - tc.rel(a, (s0 + sl) / a.C);
             double prev = ystart[(size_t)k * a.n_seq + s0 + sl];
 #pragma unroll
             for (int i = 0; i < MST_COMP_T; ++i) {
@@ -1238,6 +1294,14 @@ __global__ __launch_bounds__(256) void fx_comp_apply_kernel(CompArgs a, const do
             tile_sums[(size_t)tx * a.n_seq + s0 + threadIdx.x] = cs;
         }
     }
+}
+template <bool FILL>
+__global__ __launch_bounds__(256) void fx_comp_apply_kernel(CompArgs a, const double *yl, const double *ystart, int nchunks, int tile0, double *tile_sums) {
+    fxb_comp_apply<FILL>(a, yl, ystart, nchunks, tile0, tile_sums, FxCompCall<>{});
+}
+template <bool FILL>      // (only <true> is launched: fx_comp_apply_kernel<false> meets no time constant and serves the per-item call as it is)
+__global__ __launch_bounds__(256) void fxi_cmp_apply_kernel(CompArgs a, const double *yl, const double *ystart, int nchunks, int tile0, double *tile_sums, FxiCmpTab tb) {
+    fxb_comp_apply<FILL>(a, yl, ystart, nchunks, tile0, tile_sums, FxCompItems{tb});
 }
 
 // the per-tile partials of fx_comp_apply_kernel -> the MST_SUMSQ_SLOTS slots per item the chain fusion hands on: slot s of an item = its tiles
@@ -2139,406 +2203,4 @@ __global__ __launch_bounds__(256) void fxi_gain_kernel(const float *x, float *y,
                                                        const int *__restrict__ invert, const double *in_scale) {
     const int item = blockIdx.y;
     fxb_scale(x, y, per_item, fx_gain_factor(gain_db[item], invert ? invert[item] : 0), nullptr, nullptr, 0, per_item, in_scale);
-}
-
-// ------------------------------------------------------------------------------------------------
-// The compressor per item (mst_fx_compressor_items).  Threshold and ratio per item travel as CompArgs::thr_items / ratio_items like the
-// parameter grid's (fx_comp_curve); the attack / release coefficients and the slopes of the chunk maps' pieces come from the table
-// mst_fx_compressor_items_prepare filled on the host with the shared call's own functions.  fx_comp_gain_kernel and
-// fx_comp_apply_kernel<false> serve the split-serial form as they are (they never see a time constant).  The kernels below are
-// fx_compressor_kernel, fx_comp_smooth_kernel, fx_comp_map_kernel, fx_comp_chain_kernel and fx_comp_apply_kernel<true> step for step with
-// those values read per sequence (a chain workgroup serves one sequence: its item's slope rows are loaded once) - the shared kernels keep
-// their code and their registers, the arithmetic per sample goes through the same fx_comp_curve / fx_comp_level_diff / fx_log10_f32, and
-// tests/test_fx_items_*.py hold item i to the bits of the shared call with item i's settings.
-// ------------------------------------------------------------------------------------------------
-struct FxiCmpTab {
-    const double *aA, *aR;        // [n_items] attack / release coefficients
-    const double *slope, *inv;    // [n_items][2][MST_COMP_NP]: CompMapArgs::slope / inv_slope of the item
-    int C;
-};
-__global__ __launch_bounds__(256) void fxi_cmp_serial_kernel(CompArgs a, FxiCmpTab tb) {
-    const int lane = threadIdx.x & 63;
-    const int seq = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (seq >= a.n_seq) return;   // wave-uniform
-    const int item = seq / a.C, c = seq % a.C;
-    const double thr = a.thr_items[item], ratio = a.ratio_items[item], aatt = tb.aA[item], arel = tb.aR[item];
-    const float *xp = a.x + (size_t)item * a.L * a.C + c;
-    float *yp = a.y + (size_t)item * a.L * a.C + c;
-    double prev = 0.0;            // yL_prev is forced to 0 on entry (:553)
-    for (long n0 = 0; n0 < a.L; n0 += 64) {
-        const long n = n0 + lane;
-        const double xv = (n < a.L) ? (double)xp[n * a.C] : 0.0;
-        const double ax = fabs(xv);
-        const double xg = (ax < 0.000001) ? -120.0 : 20.0 * log10(ax);
-        double yg = 0.0;          // ratio == 1: neither branch assigns y_g (:564-573)
-        if (ratio > 1.0)
-            yg = (xg >= thr) ? thr + (xg - thr) / ratio : xg;
-        else if (ratio < 1.0)
-            yg = (xg <= thr) ? thr + (xg - thr) / (1.0 / ratio) : xg;
-        const double xl = xg - yg;
-        double yl = 0.0;
-        const int cnt = (a.L - n0) < 64 ? (int)(a.L - n0) : 64;
-        for (int i = 0; i < cnt; ++i) {
-            const double v = __shfl(xl, i);
-            if (v > prev)
-                prev = aatt * prev + (1.0 - aatt) * v;
-            else
-                prev = arel * prev + (1.0 - arel) * v;
-            if (lane == i) yl = prev;
-        }
-        if (n < a.L) yp[n * a.C] = (float)(xv * pow(10.0, (a.makeup - yl) / 20.0));
-    }
-}
-
-__global__ __launch_bounds__(64) void fxi_cmp_smooth_kernel(CompArgs a, double *xl, FxiCmpTab tb) {
-    const int seq = blockIdx.x * 64 + threadIdx.x;
-    const bool live = seq < a.n_seq;
-    // y <- alpha y + (1 - alpha) x, alpha = attack coefficient when x > y else release, evaluated as y + c (x - y) with
-    // c = 1 - alpha picked by the sign of d = x - y: three float64 operations per step (add, compare, fma) instead of five plus
-    // 64-bit address arithmetic.  A float64 VALU op issues in 8 clocks on gfx950 and the steps are one dependent chain:
-    // measured 140 clocks per step with per-lane cache lines, 99 with the time-major layout and the two-product form, 85 with
-    // this one (computing both candidates and selecting afterwards is not faster: 88).  Same value up to float64 rounding.
-    // Addresses are a uniform base + a 32-bit byte offset (scratch < 4 GiB is checked by the host).
-    unsigned char *base = (unsigned char *)xl;
-    const unsigned row = (unsigned)a.n_seq * 8u;                       // bytes per time step
-    const unsigned off0 = (unsigned)(live ? seq : a.n_seq - 1) * 8u;   // idle lanes of the last wave shadow a live one, store nothing
-    const int item = (live ? seq : a.n_seq - 1) / a.C;
-    const double ca = 1.0 - tb.aA[item], cr = 1.0 - tb.aR[item];
-    double prev = 0.0;
-    constexpr int NB = 16;
-    const long nfull = a.L / NB;
-    double nx[NB];
-    if (nfull > 0) {
-#pragma unroll
-        for (int i = 0; i < NB; ++i) nx[i] = *(const double *)(base + (size_t)(off0 + (unsigned)i * row));
-    }
-    for (long bt = 0; bt < nfull; ++bt) {
-        double v[NB];
-#pragma unroll
-        for (int i = 0; i < NB; ++i) v[i] = nx[i];
-        const unsigned nn = (unsigned)((bt + 1 < nfull) ? (bt + 1) * NB : bt * NB);      // last batch: harmless reload
-#pragma unroll
-        for (int i = 0; i < NB; ++i) nx[i] = *(const double *)(base + (size_t)(off0 + (nn + (unsigned)i) * row));
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            const double d = v[i] - prev;
-            prev = fma(d > 0.0 ? ca : cr, d, prev);
-            v[i] = prev;
-        }
-        if (live) {
-#pragma unroll
-            for (int i = 0; i < NB; ++i) *(double *)(base + (size_t)(off0 + ((unsigned)(bt * NB) + (unsigned)i) * row)) = v[i];
-        }
-    }
-    for (long n = nfull * NB; n < a.L; ++n) {
-        double *q = (double *)(base + (size_t)(off0 + (unsigned)n * row));
-        const double d = *q - prev;
-        prev = fma(d > 0.0 ? ca : cr, d, prev);
-        if (live) *q = prev;
-    }
-}
-
-// (convex and concave items share a wave: the branch of the piece update is a select per lane)
-__global__ __launch_bounds__(64) MST_HEAVY_UNROLL void fxi_cmp_map_kernel(CompMapArgs a, CompArgs ca, FxiCmpTab tb) {
-    constexpr int PASS = 16;                                        // doubles of every record that cross the LDS tile at a time (128 B)
-    __shared__ double tr[64 * (PASS + 1)];
-    __shared__ double tab[256];
-    const int k = blockIdx.x + a.chunk0;
-    const int seq = blockIdx.y * 64 + threadIdx.x;
-    const bool live = seq < a.n_seq;
-    const size_t sq = live ? seq : a.n_seq - 1;
-    // the level differences x_l are computed here from the audio (a lane walks its own sequence: 32 frames = 256 contiguous bytes that
-    // it shares with the lane of the other channel), not read from a float64 scratch that a separate pass would have to write
-    for (int i = threadIdx.x; i < 256; i += 64) tab[i] = a.log_tab[i];
-    const int item = (int)(sq / ca.C);
-    const FxCompCurve cv = fx_comp_curve(ca, item);
-    const double aA = tb.aA[item], aR = tb.aR[item], cA = 1.0 - aA, cR = 1.0 - aR;
-    const bool use_min = aA > aR;
-    const float *xp = ca.x + ((size_t)(ca.shared_x ? 0 : item) * ca.L) * ca.C + sq % ca.C;
-    __builtin_amdgcn_wave_barrier();
-    double lb[MST_COMP_NP + 1];                                     // lb[1 .. t]: the values at which the pieces meet after t steps
-    double b0 = 0.0;                                                // the lowest piece (always the attack branch); identity before step 1
-#pragma unroll
-    for (int t = 0; t < MST_COMP_T; ++t) {
-        const long n = (long)k * MST_COMP_T + t;
-        if (n < a.L) {                                              // uniform over the wave
-            const double x = fx_comp_level_diff(xp[(size_t)n * ca.C] * cv.sf, cv.thr, cv.mul, cv.mode, tab);
-            const double oA = cA * x, oR = cR * x;
-            b0 = fma(aA, b0, oA);
-            // downwards, in place: slot s reads the old slots s and s - 1.  g = f_x(old value) = max (convex) / min (concave) of the branches
-            double m = x;                                           // min(g_s, x); above the top piece: x
-#pragma unroll
-            for (int s = t + 1; s >= 1; --s) {
-                if (s > 1) {
-                    const double v = lb[s - 1];
-                    const double gA = fma(aA, v, oA), gR = fma(aR, v, oR);
-                    const double g = use_min ? fmin(gA, gR) : fmax(gA, gR);
-                    lb[s] = fmax(g, m);
-                    m = fmin(g, x);
-                } else {
-                    lb[1] = m;
-                }
-            }
-        }
-    }
-    const long left = a.L - (long)k * MST_COMP_T;
-    const int nsteps = left < MST_COMP_T ? (int)left : MST_COMP_T;  // uniform; >= 1
-    // the record (b_0, lb_1 .. lb_T, pad) leaves in passes of 16 doubles through a [lane][16 + 1] tile: every store instruction of the
-    // wave writes 128 contiguous bytes of four records
-    const int nlive = a.n_seq - blockIdx.y * 64 < 64 ? a.n_seq - blockIdx.y * 64 : 64;
-    double *row = tr + threadIdx.x * (PASS + 1);
-    double *mbase = a.maps + ((size_t)(blockIdx.y * 64) * a.nchunks + k) * MST_COMP_REC;
-    auto pass = [&](auto J) {                                       // two flat loops: both unroll early, lb stays in registers
-        constexpr int p0 = decltype(J)::value * PASS, p1 = p0 + PASS < MST_COMP_REC ? p0 + PASS : MST_COMP_REC;
-        constexpr int cnt = p1 - p0;                                // doubles in this pass
-#pragma unroll
-        for (int p = p0; p < p1; ++p) row[p - p0] = p == 0 ? b0 : ((p <= nsteps && p <= MST_COMP_T) ? lb[p <= MST_COMP_T ? p : 0] : MST_COMP_NEVER);
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int i = 0; i < cnt; ++i) {                             // 64 records x cnt doubles, lane-linear over (record, double)
-            const int idx = i * 64 + threadIdx.x, r = idx / cnt, c = idx % cnt;
-            if (r < nlive) mbase[(size_t)r * a.nchunks * MST_COMP_REC + p0 + c] = tr[r * (PASS + 1) + c];
-        }
-        __builtin_amdgcn_wave_barrier();
-    };
-    static_assert(MST_COMP_REC <= 3 * PASS, "three passes cover the record");
-    pass(std::integral_constant<int, 0>{});
-    pass(std::integral_constant<int, 1>{});
-    pass(std::integral_constant<int, 2>{});
-}
-
-__global__ __launch_bounds__(MST_CHAIN_THREADS) void fxi_cmp_chain_kernel(CompMapArgs a, FxiCmpTab tb) {
-    constexpr int CB = MST_CHAIN_CB, REC = MST_COMP_REC, NPE = MST_COMP_NP + 1, ENT = 2 * NPE;      // chunks per batch, doubles per record / per chunk of entries
-    constexpr int NH = MST_CHAIN_HELPERS, HB = CB / NH;               // helper waves; chunks per helper wave and batch
-    constexpr int NLD = (HB * REC / 2 + 63) / 64;                     // 16-byte loads per helper lane per batch
-    static_assert(REC % 2 == 0 && HB % 2 == 0, "records are whole 16-byte units; a helper takes its chunks two at a time");
-    __shared__ __attribute__((aligned(16))) double raw[NH][HB * REC];
-    __shared__ __attribute__((aligned(16))) double cooked[2][CB * ENT];      // per (chunk, piece): b, u; entry NP is never selected
-    static_assert(NH == 4, "helper waves 1, 2, 3, 5");
-    const int seq = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hw = wave == 5 ? 3 : (wave > 0 ? wave - 1 : 0);
-    const bool helper = wave != 0 && wave != 4;
-    const double *sl0 = tb.slope + (size_t)(seq / tb.C) * 2 * MST_COMP_NP, *sl1 = sl0 + MST_COMP_NP;      // the item of this sequence: its rows, once
-    const double *is0 = tb.inv + (size_t)(seq / tb.C) * 2 * MST_COMP_NP, *is1 = is0 + MST_COMP_NP;
-    const double2 *m = (const double2 *)(a.maps + (size_t)seq * a.nchunks * REC);
-    const size_t total = (size_t)a.nchunks * REC / 2;
-    const int nbatch = a.batch1;                                      // this launch walks batches batch0 .. batch1 - 1
-    // ---- waves 1, 2: global -> registers -> raw records in LDS -> entries
-    const int hp = (lane & 31) + 1;                                   // the piece this helper lane rebuilds (1 .. T)
-    const double sl_full = sl0[hp], isl_full = is0[hp - 1], sl_last = sl1[hp], isl_last = is1[hp - 1];
-    double rx[NLD], ry[NLD];                                          // (plain doubles: an array of double2 stays in scratch memory)
-    auto load = [&](int bt) {
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const size_t e = ((size_t)(bt < nbatch ? bt : nbatch - 1) * CB + hw * HB) * (REC / 2) + (size_t)i * 64 + lane;
-            const double2 v = m[e < total ? e : total - 1];
-            rx[i] = v.x;
-            ry[i] = v.y;
-        }
-    };
-    // the records of batch bt leave the registers for LDS, the loads of batch bt + 1 are issued at once (a whole batch of walking and
-    // rebuilding covers their latency), then the entries of batch bt are rebuilt
-    auto cook = [&](int buf, int bt) {
-        double2 *dst = (double2 *)raw[hw];
-#pragma unroll
-        for (int i = 0; i < NLD; ++i)
-            if (i * 64 + lane < HB * REC / 2) dst[i * 64 + lane] = double2{rx[i], ry[i]};
-        load(bt + 1);
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int it = 0; it < HB / 2; ++it) {
-            const int c = 2 * it + (lane >> 5);                       // chunk of this half-wave within the helper's share
-            const double *rec = raw[hw] + c * REC;
-            const double lbp = rec[hp], lbm = rec[hp - 1];            // rec[0] = b_0
-            const bool valid = lbp < 0.5 * MST_COMP_NEVER;            // the piece exists (the last chunk may be short)
-            const bool shortc = (long)(bt * CB + hw * HB + c + 1) * MST_COMP_T > a.L;
-            const double d = valid ? (lbp - lbm) * (shortc ? isl_last : isl_full) : 0.0;
-            const double u = mst_half_prefix_sum_f64(d);
-            double *q = cooked[buf] + ((hw * HB + c) * NPE + hp) * 2;
-            q[0] = valid ? fma(-(shortc ? sl_last : sl_full), u, lbp) : 0.0;
-            q[1] = valid ? u : MST_COMP_NEVER;
-            if (hp == 1) {                                            // the lowest piece: reached by every y
-                q[-2] = lbm;
-                q[-1] = -MST_COMP_NEVER;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    };
-    if (helper) {
-        for (int i = lane; i < 2 * HB; i += 64) {                     // the entry the lanes without a piece read: written once
-            double *q = &cooked[i / HB][((hw * HB + i % HB) * NPE + MST_COMP_NP) * 2];
-            q[0] = 0.0;
-            q[1] = MST_COMP_NEVER;
-        }
-        load(a.batch0);
-        cook(0, a.batch0);
-    }
-    __syncthreads();
-    // yL_prev = 0 on entry (common_audioeffects.py:553); a later time slice continues from the value the slice before it left
-    MstUniformF64 yu = mst_wave_read_u64(a.batch0 > 0 ? a.ycarry[seq] : 0.0, 0);
-    const int pl = lane < MST_COMP_NP ? MST_COMP_NP - 1 - lane : MST_COMP_NP;   // descending; lanes without a piece read the "never" entry
-    const double a_full = pl < MST_COMP_NP ? sl0[pl] : 0.0, a_last = pl < MST_COMP_NP ? sl1[pl] : 0.0;
-    for (int bt = a.batch0; bt < nbatch; ++bt) {
-        const int cur = (bt - a.batch0) & 1;
-        if (helper) {
-            if (bt + 1 < nbatch) {
-                cook(cur ^ 1, bt + 1);
-            }
-        } else if (wave == 0) {
-            const int nc = a.nchunks - bt * CB < CB ? a.nchunks - bt * CB : CB;
-            struct Piece { double pb, u; };
-            const double *base = cooked[cur] + 2 * pl;
-            auto fetch = [&](int c) {
-                const double2 q = *(const double2 *)(base + ENT * (c < CB ? c : CB - 1));
-                return Piece{q.x, q.y};
-            };
-            double keep = 0.0;                                      // lane c holds the start value of chunk c
-            if ((long)(bt + 1) * CB * MST_COMP_T <= a.L) {          // a whole batch of whole chunks: 32 steps in one basic block, y stays in SGPRs
-                Piece p[4];
-                p[0] = fetch(0); p[1] = fetch(1); p[2] = fetch(2);
-                yu = mst_wave_uniform(yu);
-#define MST_CHAIN_STEP(c)                                                                                              \
-    {                                                                                                                  \
-        p[((c) + 3) & 3] = fetch((c) + 3);                                                                             \
-        keep = mst_wave_park_f64<(c)>(keep, yu);                                                                       \
-        const Piece &q = p[(c) & 3];                                                                                   \
-        yu = mst_wave_first_ge(yu, q.u, fma(a_full, yu.value(), q.pb));                                                \
-    }
-#define MST_CHAIN_STEP8(c) MST_CHAIN_STEP(c) MST_CHAIN_STEP((c) + 1) MST_CHAIN_STEP((c) + 2) MST_CHAIN_STEP((c) + 3) \
-    MST_CHAIN_STEP((c) + 4) MST_CHAIN_STEP((c) + 5) MST_CHAIN_STEP((c) + 6) MST_CHAIN_STEP((c) + 7)
-                static_assert(CB == 32, "four groups of eight steps");
-                MST_CHAIN_STEP8(0) MST_CHAIN_STEP8(8) MST_CHAIN_STEP8(16) MST_CHAIN_STEP8(24)
-#undef MST_CHAIN_STEP8
-#undef MST_CHAIN_STEP
-            } else {                                                // the last batch: ragged, or its last chunk is short
-                for (int c = 0; c < nc; ++c) {
-                    const Piece q = fetch(c);
-                    const double y = yu.value();
-                    keep = lane == c ? y : keep;
-                    const double sa = (long)(bt * CB + c + 1) * MST_COMP_T > a.L ? a_last : a_full;
-                    yu = mst_wave_first_ge(yu, q.u, fma(sa, y, q.pb));
-                }
-            }
-            if (lane < nc) a.ystart[(size_t)(bt * CB + lane) * a.n_seq + seq] = keep;
-            if (bt + 1 == nbatch && lane == 0) a.ycarry[seq] = yu.value();
-        }
-        __syncthreads();
-    }
-}
-
-template <bool FILL>
-__global__ __launch_bounds__(256) void fxi_cmp_apply_kernel(CompArgs a, const double *yl, const double *ystart, int nchunks, int tile0, double *tile_sums, FxiCmpTab tb) {
-    __shared__ double t[64][65];
-    const long tx = (long)blockIdx.x + tile0;                       // time tile (a launch covers the tiles of one time slice)
-    const long n0 = tx * 64;
-    const int s0 = blockIdx.y * 64;
-    float xv[16];
-    if constexpr (FILL) {
-        static_assert(MST_COMP_T == 32, "two chunks per 64-step tile");
-        // yl = the log10 table: the level differences are recomputed from the audio (audio side: lanes along time), the smoother runs
-        // along time in LDS (sequence side), the result stays in the tile for the gain application below
-        __shared__ double tab[256];
-        __shared__ double sthr[64], smul[64];
-        __shared__ int smode[64];
-        __shared__ float ssf[64];
-        tab[threadIdx.x] = yl[threadIdx.x];
-        if (threadIdx.x < 64) {
-            const int seq = s0 + threadIdx.x < a.n_seq ? s0 + threadIdx.x : a.n_seq - 1;
-            const FxCompCurve c = fx_comp_curve(a, seq / a.C);
-            sthr[threadIdx.x] = c.thr; smul[threadIdx.x] = c.mul; smode[threadIdx.x] = c.mode; ssf[threadIdx.x] = c.sf;
-        }
-        // this thread's 16 samples (scaled), all loads in flight before the first use; kept in registers for the gain application
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int idx = k * 256 + threadIdx.x, sq = s0 + (idx >> 6);
-            const long n = n0 + (idx & 63);
-            const bool ok = sq < a.n_seq && n < a.L;
-            const int sc = ok ? sq : 0;
-            xv[k] = a.x[((size_t)(a.shared_x ? 0 : sc / a.C) * a.L + (ok ? n : 0)) * a.C + sc % a.C];      // never a predicated load
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {                               // (full unroll: xv stays in registers)
-            const int idx = k * 256 + threadIdx.x, sl = idx >> 6, nl = idx & 63;
-            xv[k] *= ssf[sl];
-            t[nl][sl] = (s0 + sl < a.n_seq && n0 + nl < a.L) ? fx_comp_level_diff(xv[k], sthr[sl], smul[sl], smode[sl], tab) : 0.0;
-        }
-        __syncthreads();
-        const int sl = threadIdx.x & 63, hh = threadIdx.x >> 6;
-        const long k = tx * 2 + hh;
-        if (hh < 2 && s0 + sl < a.n_seq && k < nchunks) {
-            const double cA = 1.0 - tb.aA[(s0 + sl) / a.C], cR = 1.0 - tb.aR[(s0 + sl) / a.C];
-            double prev = ystart[(size_t)k * a.n_seq + s0 + sl];
-#pragma unroll
-            for (int i = 0; i < MST_COMP_T; ++i) {
-                const double d = t[hh * MST_COMP_T + i][sl] - prev;
-                prev = fma(d > 0.0 ? cA : cR, d, prev);
-                t[hh * MST_COMP_T + i][sl] = prev;
-            }
-        }
-    } else {
-#pragma unroll 4
-        for (int k = 0; k < 16; ++k) {
-            const int idx = k * 256 + threadIdx.x, nl = idx >> 6, sl = idx & 63;
-            t[nl][sl] = (s0 + sl < a.n_seq && n0 + nl < a.L) ? yl[(size_t)(n0 + nl) * a.n_seq + s0 + sl] : 0.0;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const int idx = k * 256 + threadIdx.x, sl = idx >> 6, nl = idx & 63;
-        const int seq = s0 + sl;
-        const long n = n0 + nl;
-        if (seq < a.n_seq && n < a.L) {
-            const size_t e = ((size_t)(seq / a.C) * a.L + n) * a.C + seq % a.C;
-            const size_t ex = a.shared_x ? (size_t)n * a.C + seq % a.C : e;
-            const float xs = FILL ? xv[k] : a.x[ex] * (a.in_scale ? (float)a.in_scale[seq / a.C] : 1.0f);
-            // 10^(v / 20) as exp(v ln10 / 20): the general pow() is five times the instructions for the same value to 1e-15 relative
-            const float out = (float)((double)xs * exp((a.makeup - t[nl][sl]) * 0.11512925464970228420));
-            a.y[e] = out;
-            if (a.out_sumsq) t[nl][sl] = a.out_ms ? (double)out : (double)out * (double)out;      // this thread's own tile element: reused for the energy sums
-        } else if (a.out_sumsq) {
-            t[nl][sl] = 0.0;
-        }
-    }
-    if (a.out_sumsq && a.out_ms) {
-        // stereo chain, an imager downstream: the tile holds the OUTPUT samples (exact float32 values); thread (pair p = tid & 31, frames
-        // nl = 8 (tid >> 5) .. + 7) forms l^2 + r^2 and the imager's mid / side terms - m = l + r, s = l - r and their squares in float32,
-        // sums in float64, like fx_energy_parts_kernel - then lanes p and p + 32 meet by a shuffle, the four waves through LDS, and pair p
-        // writes the tile's three partial sums of its item (C == 2: the tile's sequences 2 p, 2 p + 1 are the channels of one item)
-        __shared__ double red[4][32][3];
-        __syncthreads();
-        const int p = threadIdx.x & 31, g8 = threadIdx.x >> 5;
-        double e2 = 0.0, em = 0.0, es = 0.0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float l = (float)t[8 * g8 + i][2 * p], r = (float)t[8 * g8 + i][2 * p + 1];
-            const float m = l + r, sd = l - r;
-            e2 += (double)l * (double)l + (double)r * (double)r;
-            em += (double)(m * m);
-            es += (double)(sd * sd);
-        }
-        e2 += __shfl_xor(e2, 32);
-        em += __shfl_xor(em, 32);
-        es += __shfl_xor(es, 32);
-        if ((threadIdx.x & 63) < 32) {
-            red[threadIdx.x >> 6][p][0] = e2;
-            red[threadIdx.x >> 6][p][1] = em;
-            red[threadIdx.x >> 6][p][2] = es;
-        }
-        __syncthreads();
-        if (threadIdx.x < 32 && s0 + 2 * p < a.n_seq) {
-            double *q = tile_sums + ((size_t)tx * (a.n_seq / 2) + (s0 + 2 * p) / 2) * 3;
-            q[0] = (red[0][p][0] + red[1][p][0]) + (red[2][p][0] + red[3][p][0]);
-            q[1] = (red[0][p][1] + red[1][p][1]) + (red[2][p][1] + red[3][p][1]);
-            q[2] = (red[0][p][2] + red[1][p][2]) + (red[2][p][2] + red[3][p][2]);
-        }
-    } else if (a.out_sumsq) {             // column sums of the tile: one partial per (tile, sequence); the reduction adds the channels of an item
-        __syncthreads();
-        if (threadIdx.x < 64 && s0 + (int)threadIdx.x < a.n_seq) {
-            double cs = 0.0;
-#pragma unroll 8
-            for (int nl = 0; nl < 64; ++nl) cs += t[nl][threadIdx.x];
-            tile_sums[(size_t)tx * a.n_seq + s0 + threadIdx.x] = cs;
-        }
-    }
 }

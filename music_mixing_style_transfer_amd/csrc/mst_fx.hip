@@ -608,8 +608,6 @@ FxSide *fx_side() {
     return sides[dev];
 }
 
-// items: mst_fx_compressor_items - attack / release coefficients and slope rows per item from the prepared table (every item vetted by
-// mst_fx_compressor_items_prepare: no serial-only dispatch here), the same launches with the per-item kernels
 // the slope of the piece at sorted position p of a chunk map and its reciprocal; [0]: a chunk of T steps, [1]: a last chunk of n_last steps
 void comp_slopes(double aA, double aR, int n_last, double (*slope)[MST_COMP_NP], double (*inv_slope)[MST_COMP_NP]) {
     for (int which = 0; which < 2; ++which) {
@@ -621,16 +619,22 @@ void comp_slopes(double aA, double aR, int n_last, double (*slope)[MST_COMP_NP],
     }
 }
 
+// items: mst_fx_compressor_items - attack / release coefficients and slope rows per item from the prepared table (every item vetted by
+// mst_fx_compressor_items_prepare: no serial-only dispatch here), the same launches with the per-item kernels
 int compressor_run(CompArgs a, int n_items, long L, int C, double *scratch, size_t scratch_bytes, void *stream, bool slice_small = false,
                    const FxiCmpTab *items = nullptr) {
+    // a pass that meets a time constant has two kernels over one body (fx_kernels.h, fxb_comp_*): the per-item one takes the table last
+    auto launch = [&](auto *shared, auto *per_item, dim3 grid, dim3 block, void *st, auto... args) {
+        if (items) MST_LAUNCH(per_item, grid, block, st, args..., *items);
+        else MST_LAUNCH(shared, grid, block, st, args...);
+    };
     // the time-parallel smoother only where its chunk maps are well conditioned (one host comparison, comp_well_conditioned); beyond, the plain
     // call runs one wave per sequence; a call that form cannot serve (chain fusion, parameter grid) is refused, never answered with garbage
     const bool serial_only = !items && (L + MST_COMP_T - 1) / MST_COMP_T >= 4 && !comp_well_conditioned(a.alpha_att, a.alpha_rel, L);
     if (serial_only && (a.thr_items || a.in_scale || a.out_sumsq))
         return fail(MST_ERR_UNSUPPORTED, comp_refusal(a.thr_items ? "mst_fx_compressor_grid" : "mst_fx_compressor", a.alpha_att, a.alpha_rel, L));
     if (!scratch || serial_only) {
-        if (items) MST_LAUNCH(fxi_cmp_serial_kernel, dim3((a.n_seq + 3) / 4), dim3(256), stream, a, *items);
-        else MST_LAUNCH(fx_compressor_kernel, dim3((a.n_seq + 3) / 4), dim3(256), stream, a);
+        launch(fx_compressor_kernel, fxi_cmp_serial_kernel, dim3((a.n_seq + 3) / 4), dim3(256), stream, a);
         MST_CHECK_LAUNCH("fx_compressor_kernel");
         return MST_OK;
     }
@@ -651,8 +655,7 @@ int compressor_run(CompArgs a, int n_items, long L, int C, double *scratch, size
     if (cs.nchunks < 4) {                               // very short signals: level differences, serial smoother, gain application
         MST_LAUNCH(fx_comp_gain_kernel, tiles, dim3(256), stream, a, scratch);
         MST_CHECK_LAUNCH("fx_comp_gain_kernel");
-        if (items) MST_LAUNCH(fxi_cmp_smooth_kernel, dim3((a.n_seq + 63) / 64), dim3(64), stream, a, scratch, *items);
-        else MST_LAUNCH(fx_comp_smooth_kernel, dim3((a.n_seq + 63) / 64), dim3(64), stream, a, scratch);
+        launch(fx_comp_smooth_kernel, fxi_cmp_smooth_kernel, dim3((a.n_seq + 63) / 64), dim3(64), stream, a, scratch);
         MST_CHECK_LAUNCH("fx_comp_smooth_kernel");
         MST_LAUNCH((fx_comp_apply_kernel<false>), tiles, dim3(256), stream, a, (const double *)scratch, (const double *)nullptr, 0, 0, tsums);
         MST_CHECK_LAUNCH("fx_comp_apply_kernel");
@@ -694,9 +697,7 @@ int compressor_run(CompArgs a, int n_items, long L, int C, double *scratch, size
         mm.chunk0 = b0 * MST_CHAIN_CB;
         const long c1 = std::min<long>((long)b1 * MST_CHAIN_CB, cs.nchunks);
         const dim3 cg((unsigned)(c1 - mm.chunk0), (unsigned)gy);
-        if (items) MST_LAUNCH(fxi_cmp_map_kernel, cg, dim3(64), st, mm, a, *items);
-        else if (m.use_min) MST_LAUNCH(fx_comp_map_kernel<true>, cg, dim3(64), st, mm, a);
-        else MST_LAUNCH(fx_comp_map_kernel<false>, cg, dim3(64), st, mm, a);
+        launch(m.use_min ? fx_comp_map_kernel<true> : fx_comp_map_kernel<false>, fxi_cmp_map_kernel, cg, dim3(64), st, mm, a);
         MST_CHECK_LAUNCH("fx_comp_map_kernel");
         return MST_OK;
     };
@@ -704,15 +705,13 @@ int compressor_run(CompArgs a, int n_items, long L, int C, double *scratch, size
         CompMapArgs mm = m;
         mm.batch0 = b0;
         mm.batch1 = b1;
-        if (items) MST_LAUNCH(fxi_cmp_chain_kernel, dim3(a.n_seq), dim3(MST_CHAIN_THREADS), st, mm, *items);
-        else MST_LAUNCH(fx_comp_chain_kernel, dim3(a.n_seq), dim3(MST_CHAIN_THREADS), st, mm);
+        launch(fx_comp_chain_kernel, fxi_cmp_chain_kernel, dim3(a.n_seq), dim3(MST_CHAIN_THREADS), st, mm);
         MST_CHECK_LAUNCH("fx_comp_chain_kernel");
         return MST_OK;
     };
     auto launch_apply = [&](int b0, int b1, void *st) -> int {      // a batch is 32 chunks = 16 time tiles of 64 samples
         const long t0 = (long)b0 * (MST_CHAIN_CB / 2), t1 = std::min<long>((long)b1 * (MST_CHAIN_CB / 2), (long)tiles.x);
-        if (items) MST_LAUNCH((fxi_cmp_apply_kernel<true>), dim3((unsigned)(t1 - t0), tiles.y), dim3(256), st, a, tab, (const double *)m.ystart, m.nchunks, (int)t0, tsums, *items);
-        else MST_LAUNCH((fx_comp_apply_kernel<true>), dim3((unsigned)(t1 - t0), tiles.y), dim3(256), st, a, tab, (const double *)m.ystart, m.nchunks, (int)t0, tsums);
+        launch(fx_comp_apply_kernel<true>, fxi_cmp_apply_kernel<true>, dim3((unsigned)(t1 - t0), tiles.y), dim3(256), st, a, tab, (const double *)m.ystart, m.nchunks, (int)t0, tsums);
         MST_CHECK_LAUNCH("fx_comp_apply_kernel");
         return MST_OK;
     };
@@ -945,26 +944,43 @@ int energy(const float *x, double *acc, int n_items, long per_item, int mode, vo
     MST_CHECK_LAUNCH("fx_energy_kernel");
     return MST_OK;
 }
+
+// what mst_fx_midside_imager and mst_fx_midside_imager_items (who) do ahead of their apply launch: the refusals of a fuse they cannot serve,
+// then the mid / side energy parts the apply pass reads
+int imager_parts(const char *who, const float *x, int n_items, long L, double *scratch, const MstFxFuse *fuse, void *stream, const double **parts,
+                 int *chunks) {
+    if (int rc = fuse_check(fuse, who)) return rc;
+    if (fuse && fuse->out_in_sumsq_dev) return fail(MST_ERR_UNSUPPORTED, std::string(who) + ": out_in_sumsq_dev is the equaliser's");
+    if (fuse && fuse->post_rms && !fuse->in_sumsq_dev) return fail(MST_ERR_ARG, std::string(who) + ": post_rms needs in_sumsq_dev");
+    if (fuse && fuse->out_ms_dev) return fail(MST_ERR_UNSUPPORTED, std::string(who) + ": out_ms_dev is the compressor's");
+    *chunks = (int)std::min<long>(MST_SUMSQ_SLOTS, (L + 8191) / 8192);
+    if (*chunks < 1) *chunks = 1;
+    *parts = scratch;
+    if (fuse && fuse->in_ms_dev) {          // the producer of x (the compressor's apply pass) left the mid / side energies behind: no energy pass
+        *parts = fuse->in_ms_dev;
+        *chunks = MST_SUMSQ_SLOTS;
+    } else {
+        MST_LAUNCH(fx_energy_parts_kernel, dim3(n_items * *chunks), dim3(256), stream, x, scratch, L, *chunks);
+        MST_CHECK_LAUNCH("fx_energy_parts_kernel");
+    }
+    return MST_OK;
+}
+// mst_fx_gain and mst_fx_gain_items (who) take in_scale_dev from a fuse and nothing else
+int gain_fuse_check(const MstFxFuse *fuse, const char *who) {
+    if (int rc = fuse_check(fuse, who)) return rc;
+    if (fuse && (fuse->post_rms || fuse->out_in_sumsq_dev || fuse->out_ms_dev || fuse->in_ms_dev))
+        return fail(MST_ERR_UNSUPPORTED, std::string(who) + ": tail folding (post_rms) is the imager's, out_in_sumsq_dev the equaliser's, the mid / side energies the compressor's / imager's");
+    return MST_OK;
+}
 }  // namespace
 
 extern "C" int mst_fx_midside_imager(const float *x, float *y, int n_items, long L, double bal, double *scratch, const MstFxFuse *fuse,
                                      void *stream) {
     if (!x || !y || !scratch || n_items < 1 || L < 1) return fail(MST_ERR_ARG, "mst_fx_midside_imager: bad argument");
-    if (int rc = fuse_check(fuse, "mst_fx_midside_imager")) return rc;
+    const double *parts;
+    int chunks;
+    if (int rc = imager_parts("mst_fx_midside_imager", x, n_items, L, scratch, fuse, stream, &parts, &chunks)) return rc;
     const bool fold = fuse && fuse->post_rms;
-    if (fuse && fuse->out_in_sumsq_dev) return fail(MST_ERR_UNSUPPORTED, "mst_fx_midside_imager: out_in_sumsq_dev is the equaliser's");
-    if (fold && !fuse->in_sumsq_dev) return fail(MST_ERR_ARG, "mst_fx_midside_imager: post_rms needs in_sumsq_dev");
-    if (fuse && fuse->out_ms_dev) return fail(MST_ERR_UNSUPPORTED, "mst_fx_midside_imager: out_ms_dev is the compressor's");
-    int chunks = (int)std::min<long>(MST_SUMSQ_SLOTS, (L + 8191) / 8192);
-    if (chunks < 1) chunks = 1;
-    const double *parts = scratch;
-    if (fuse && fuse->in_ms_dev) {          // the producer of x (the compressor's apply pass) left the mid / side energies behind: no energy pass
-        parts = fuse->in_ms_dev;
-        chunks = MST_SUMSQ_SLOTS;
-    } else {
-        MST_LAUNCH(fx_energy_parts_kernel, dim3(n_items * chunks), dim3(256), stream, x, scratch, L, chunks);
-        MST_CHECK_LAUNCH("fx_energy_parts_kernel");
-    }
     const double bal_r = std::round(bal * 1000.0) / 1000.0;   // round(bal, 3) (:980)
     MST_LAUNCH(fx_imager_apply_kernel, dim3((unsigned)((L + MST_IMAGER_FRAMES - 1) / MST_IMAGER_FRAMES), n_items), dim3(256), stream, x, y,
                parts, chunks, L, bal_r, fuse ? fuse->in_scale_dev : (const double *)nullptr,
@@ -977,9 +993,7 @@ extern "C" int mst_fx_midside_imager(const float *x, float *y, int n_items, long
 extern "C" int mst_fx_gain(const float *x, float *y, int n_items, long L, int C, double gain_db, int invert, const MstFxFuse *fuse,
                            void *stream) {
     if (!x || !y || n_items < 1 || L < 1 || C < 1) return fail(MST_ERR_ARG, "mst_fx_gain: bad argument");
-    if (int rc = fuse_check(fuse, "mst_fx_gain")) return rc;
-    if (fuse && (fuse->post_rms || fuse->out_in_sumsq_dev || fuse->out_ms_dev || fuse->in_ms_dev))
-        return fail(MST_ERR_UNSUPPORTED, "mst_fx_gain: tail folding (post_rms) is the imager's, out_in_sumsq_dev the equaliser's, the mid / side energies the compressor's / imager's");
+    if (int rc = gain_fuse_check(fuse, "mst_fx_gain")) return rc;
     const long per = L * C;
     MST_LAUNCH(fx_scale_kernel, dim3((unsigned)((per + 255) / 256), n_items), dim3(256), stream, x, y, per, fx_gain_factor(gain_db, invert),
                (const double *)nullptr, (const double *)nullptr, 0, per, fuse ? fuse->in_scale_dev : (const double *)nullptr);
@@ -990,21 +1004,10 @@ extern "C" int mst_fx_gain(const float *x, float *y, int n_items, long L, int C,
 extern "C" int mst_fx_midside_imager_items(const float *x, float *y, int n_items, long L, const double *bal_dev, double *scratch,
                                            const float *post_gain_dev, const MstFxFuse *fuse, void *stream) {
     if (!x || !y || !scratch || !bal_dev || n_items < 1 || n_items > 65535 || L < 1) return fail(MST_ERR_ARG, "mst_fx_midside_imager_items: bad argument");
-    if (int rc = fuse_check(fuse, "mst_fx_midside_imager_items")) return rc;
+    const double *parts;
+    int chunks;
+    if (int rc = imager_parts("mst_fx_midside_imager_items", x, n_items, L, scratch, fuse, stream, &parts, &chunks)) return rc;
     const bool fold = fuse && fuse->post_rms;
-    if (fuse && fuse->out_in_sumsq_dev) return fail(MST_ERR_UNSUPPORTED, "mst_fx_midside_imager_items: out_in_sumsq_dev is the equaliser's");
-    if (fold && !fuse->in_sumsq_dev) return fail(MST_ERR_ARG, "mst_fx_midside_imager_items: post_rms needs in_sumsq_dev");
-    if (fuse && fuse->out_ms_dev) return fail(MST_ERR_UNSUPPORTED, "mst_fx_midside_imager_items: out_ms_dev is the compressor's");
-    int chunks = (int)std::min<long>(MST_SUMSQ_SLOTS, (L + 8191) / 8192);
-    if (chunks < 1) chunks = 1;
-    const double *parts = scratch;
-    if (fuse && fuse->in_ms_dev) {
-        parts = fuse->in_ms_dev;
-        chunks = MST_SUMSQ_SLOTS;
-    } else {
-        MST_LAUNCH(fx_energy_parts_kernel, dim3(n_items * chunks), dim3(256), stream, x, scratch, L, chunks);
-        MST_CHECK_LAUNCH("fx_energy_parts_kernel");
-    }
     MST_LAUNCH(fxi_imager_apply_kernel, dim3((unsigned)((L + MST_IMAGER_FRAMES - 1) / MST_IMAGER_FRAMES), n_items), dim3(256), stream, x, y,
                parts, chunks, L, bal_dev, fuse ? fuse->in_scale_dev : (const double *)nullptr,
                fuse ? fuse->out_sumsq_dev : (double *)nullptr, fold ? fuse->in_sumsq_dev : (const double *)nullptr,
@@ -1016,9 +1019,7 @@ extern "C" int mst_fx_midside_imager_items(const float *x, float *y, int n_items
 extern "C" int mst_fx_gain_items(const float *x, float *y, int n_items, long L, int C, const double *gain_db_dev, const int *invert_dev,
                                  const MstFxFuse *fuse, void *stream) {
     if (!x || !y || !gain_db_dev || n_items < 1 || n_items > 65535 || L < 1 || C < 1) return fail(MST_ERR_ARG, "mst_fx_gain_items: bad argument");
-    if (int rc = fuse_check(fuse, "mst_fx_gain_items")) return rc;
-    if (fuse && (fuse->post_rms || fuse->out_in_sumsq_dev || fuse->out_ms_dev || fuse->in_ms_dev))
-        return fail(MST_ERR_UNSUPPORTED, "mst_fx_gain_items: tail folding (post_rms) is the imager's, out_in_sumsq_dev the equaliser's, the mid / side energies the compressor's / imager's");
+    if (int rc = gain_fuse_check(fuse, "mst_fx_gain_items")) return rc;
     const long per = L * C;
     MST_LAUNCH(fxi_gain_kernel, dim3((unsigned)((per + 255) / 256), n_items), dim3(256), stream, x, y, per, gain_db_dev, invert_dev,
                fuse ? fuse->in_scale_dev : (const double *)nullptr);
